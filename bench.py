@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — frames/sec end-to-end (extract + fuse + score) on synthetic 224x224x3 frames + 16 kHz audio.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Headline workload at N=1 = BASELINE.json configs[1]: SumMe-shape batch, 25 videos x ~1.8k frames (lengths
 ~N(1800,300) clipped to [900,2700], seed 2002), visual-only (audio = the literal zeros(296)), ResNet-50
@@ -16,17 +16,24 @@ every rank runs its own batch of the same shape (weak scaling; videos are indepe
 collective) and the per-video scores are all-gathered (C2) inside the timed region.  `--config 3` runs one rank's
 share of configs[3] instead (50 videos x 5000 frames per rank).
 
-ONE JSON line on rank 0 (contract in the task description) with, beside the headline:
+ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times the K steps, writes
+the last timed step's outputs if --dump-outputs is given, and prints the line: the headline only, its roofline,
+cpu_baseline, accuracy and sub_results null.  --full adds, beside the headline:
   roofline      the dominant kernel (implicit-GEMM conv, MFMA-bound): algorithmic FLOPs of all its launches in the
                 timed region / their summed HIP-event durations (events on the launch stream);
   cpu_baseline  the oracle (CPU restatement of the same path) on bounded samples, median of --cpu-runs runs;
   accuracy      the benchmarked arithmetic mode against the fp32 oracle on those same samples: score error,
                 selection agreement, F1 drift, and whether north_star's bars (1e-4 / 0.001) are met by THIS mode;
-  sub_results   (N=1, default on) the other claimed configurations, each timed the same way with fewer steps:
+  sub_results   (N=1, with the default headline) the other claimed configurations, each timed the same way with fewer steps:
                 the bf16 throughput mode, the reference's 4-frame micro-batches, both trunks, the exact-fp32 and
                 fp32-split modes (each with its own roofline block), a PCIe-inclusive pass (pinned host frames,
                 upload overlapped with compute), the configs[2] audio+visual+fusion leg with the audio kernels' HBM
-                roofline, one rank's configs[3] share.
+                roofline, one rank's configs[3] share, the configs[4] training leg.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step (rank 0's share), as float32 .npy files:
+scores.npy (the per-frame importance scores, [frames]) and selected_mask.npy (1.0 where the selection rule keeps the
+frame); --config 2: the same per shot; --config 4: loss_t<T>.npy, the last step's loss per sequence length (float64).
+Inputs and weights are seeded, so two runs with the same arguments see the same inputs.
 """
 import argparse
 import json
@@ -213,13 +220,50 @@ def pmc_traffic(mode):
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each array of `arrays` ({name: 1-D float32 / float64 numpy array}, all of one length) as out_dir/<name>.npy.
+    Past `limit` bytes in all, the same fixed, seeded sample of positions is taken from every array and its positions
+    are written beside them (sample_index.npy, float64).  Returns the names written."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64) or v.ndim != 1:
+            raise ValueError(f"--dump-outputs: {k} is {v.dtype} {v.shape}, not a 1-D float32 / float64 array")
+    n = {v.shape[0] for v in arrays.values()}
+    if len(n) != 1:
+        raise ValueError(f"--dump-outputs: arrays of different lengths {sorted(n)}")
+    n = n.pop()
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit:
+        keep = limit * n // (total + 8 * n)   # bytes per kept position: the arrays' + 8 for its float64 position
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
+    return sorted(arrays)
+
+
+def selection_mask(selected, offsets):
+    """The per-video selected indices (FrameScoringPipeline.select) as one float32 0 / 1 mask over the frames."""
+    mask = np.zeros(offsets[-1], dtype=np.float32)
+    for a, sel in zip(offsets[:-1], selected):
+        mask[a + np.asarray(sel, dtype=np.int64)] = 1.0
+    return mask
+
+
 # ------------------------------------------------------------------------------------------------ configs[2] leg
-def config2_leg(extractor, scorer, dev, steps, videos):
+def config2_leg(extractor, scorer, dev, steps, videos, outputs=None):
     """configs[2] (TVSum shape): per video the whole-track log2-mel and MFCC (+ mfcc_proj) kernels
     (features/extractors.py:236-246), CNN embeddings of the frames the reference's sampling rule keeps (30-frame
     shots, absolute index % 3 == 0, mean over a shot, :395-413, :97-110), an audio vector per shot pooled from the
     track's frames, features/fusion.py (cost matrix float64, warping path, path-weighted gather, fusion.py:7-32) on
-    the two 512-d embedded streams, then the scorer and the selection."""
+    the two 512-d embedded streams, then the scorer and the selection.  outputs (a dict): receives the last step's
+    per-shot scores and selection mask (--dump-outputs)."""
     from avsum_amd import ops, synthetic
     from avsum_amd.audio import HOP, MelPlan
     from avsum_amd.features import fusion
@@ -256,6 +300,7 @@ def config2_leg(extractor, scorer, dev, steps, videos):
     runner = extractor._resnet_runner
     vfc, afc = scorer.visual_fc[0], scorer.audio_fc[0]
     audio_ms = [0.0]
+    last_host = [None]
 
     def step():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -289,6 +334,7 @@ def config2_leg(extractor, scorer, dev, steps, videos):
         seq = torch.tensor(shot_rows, dtype=torch.int64, device=dev)
         scores = scorer.score_rows(visual, audio296, seq, attn_batch=1)
         host = scores.cpu().numpy()
+        last_host[0] = host
         sel = sum(int((host[a:b] > host[a:b].mean()).sum()) for a, b in zip(shot_rows[:-1], shot_rows[1:]))
         audio_ms[0] += e0.elapsed_time(e1)
         return sel, fused_rows
@@ -302,6 +348,11 @@ def config2_leg(extractor, scorer, dev, steps, videos):
             sel, fused_rows = step()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+    if outputs is not None:
+        host = last_host[0]
+        outputs["scores"] = host.astype(np.float32)
+        outputs["selected_mask"] = np.concatenate([(host[a:b] > host[a:b].mean()).astype(np.float32)
+                                                   for a, b in zip(shot_rows[:-1], shot_rows[1:])])
     stft_frames = sum(1 + w.numel() // HOP for w in waves)
     # 4 B per sample read; "if time-mean pooled on-chip, output ~ 0": the two per-shot [shots, 128] means
     algo_bytes = 4.0 * samples + 2 * 512.0 * shots
@@ -326,7 +377,7 @@ def config2_leg(extractor, scorer, dev, steps, videos):
 
 
 # ------------------------------------------------------------------------------------------------ configs[4] leg
-def config4_leg(dev, steps=20, lengths=(300, 1800), oracle_steps=6, rank=0, world=1):
+def config4_leg(dev, steps=20, lengths=(300, 1800), oracle_steps=6, rank=0, world=1, outputs=None):
     """configs[4] (scripts/train_av_model.py:70-96 on synthetic labels) at world size 1: the reference's training step -
     Dropout active, forward, MSE against the one broadcast target, loss.backward(), AdamW(lr 1e-4).step() - for `steps`
     steps per sequence length, every step through avsum_amd.scripts.train_av_model.train_step (forward and backward are
@@ -337,7 +388,8 @@ def config4_leg(dev, steps=20, lengths=(300, 1800), oracle_steps=6, rank=0, worl
     world > 1 (launched with torch.distributed.run, one rank per GPU): plain data parallelism as SURVEY 8 E1 states it - every
     rank takes its own video per step, train_step averages the gradients over the ranks (dist.allreduce_gradients: one RCCL
     all-reduce of the 38.7 MB bucket) before AdamW; videos per second = world x steps per second.  The loss trajectory against
-    the oracle is a world-1 statement (the effective batch differs) and is skipped."""
+    the oracle is a world-1 statement (the effective batch differs) and is skipped.  outputs (a dict): receives the loss of
+    the last timed step of every length (--dump-outputs)."""
     from avsum_amd import _abi, ops
     from avsum_amd.models.av_model import AVBiLSTMModel
     from avsum_amd.scripts.train_av_model import train_step
@@ -364,6 +416,8 @@ def config4_leg(dev, steps=20, lengths=(300, 1800), oracle_steps=6, rank=0, worl
         if world > 1:
             torch.distributed.barrier()
         dt = time.perf_counter() - t0
+        if outputs is not None:
+            outputs[f"loss_t{t_len}"] = np.array([loss], dtype=np.float64)
         if world > 1:
             tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
             torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
@@ -455,7 +509,7 @@ def config4_leg(dev, steps=20, lengths=(300, 1800), oracle_steps=6, rank=0, worl
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 5; --config 4: 20 per sequence length)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", type=int, default=1, choices=[1, 2, 3, 4],
                     help="BASELINE config of the headline: 1 = SumMe-shape batch per rank; 2 = the TVSum-shape "
@@ -475,15 +529,23 @@ def main():
     ap.add_argument("--streams", type=int, default=1, choices=[1, 2],
                     help="2: consecutive passes of the trunk on two HIP streams, staggered by half a pass (the HBM-bound "
                          "layers 1-2 of one pass under the matrix-core-bound layers 3-4 of the other)")
-    ap.add_argument("--cpu-sample", type=int, default=128, help="frames per CPU-baseline run (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: the live roofline (HIP events on the timed "
+                         "launches), the CPU baseline and the accuracy of the timed mode, and (default headline, N=1) the "
+                         "sub-results.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="frames per CPU-baseline run (0 = skip; default: 128 with --full, 0 without)")
     ap.add_argument("--cpu-runs", type=int, default=5, help="CPU-baseline runs (the median is reported)")
     ap.add_argument("--frames-per-group", type=int, default=4,
                     help="BatchNorm micro-batch inside a video: 4 (default) = frames normalised in the reference's "
                          "micro-batches of 4 consecutive frames (extractors.py:48-56; a video's last group is shorter), "
                          "per-frame scores; 1 = every frame its own one-frame shot (= its own micro-batch)")
-    ap.add_argument("--sub", default="auto", choices=["auto", "all", "none"],
-                    help="sub-results (other configurations): auto = all of them at N=1 with the default headline")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--sub", default=None, choices=["auto", "all", "none"],
+                    help="sub-results (other configurations): auto = all of them at N=1 with the default headline "
+                         "(default: auto with --full, none without)")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the live roofline's HIP events")
     ap.add_argument("--profile-every", type=int, default=1,
                     help="bracket every n-th launch of each kernel kind with HIP events (1 = all: ~3%% slower at "
                          "small passes, nothing at 12288 frames)")
@@ -493,6 +555,13 @@ def main():
                     help="tuning (f16x2): the inner block outputs of ResNet layers 1-2 stored as AVS_F16P8 (3 bytes per value)")
     ap.add_argument("--fuse", default=None, help="tuning: min_rows,ratio_num,ratio_den of the one-kernel conv+BN")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 20 if args.config == 4 else 5
+    if args.cpu_sample is None:
+        args.cpu_sample = 128 if args.full else 0
+    if args.sub is None:
+        args.sub = "auto" if args.full else "none"
+    dumped = {} if args.dump_outputs else None
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the documented launcher as a CHILD process (this
@@ -566,9 +635,11 @@ def main():
 
     if args.config == 4:
         # the configs[4] training leg on its own (what sub_results.config4_training runs at N = 1); N > 1: data-parallel
-        c4_steps = args.steps if args.steps != 5 else 20
-        leg = config4_leg(dev, steps=c4_steps, rank=rank, world=world)
+        c4_steps = args.steps
+        leg = config4_leg(dev, steps=c4_steps, rank=rank, world=world, outputs=dumped)
         if rank == 0:
+            if dumped is not None:
+                dump_outputs(args.dump_outputs, dumped)
             best = leg["lengths"]["1800"]
             print(json.dumps({"metric": "training videos/sec (scripts/train_av_model.py loop, T = 1800, data-parallel over the ranks)",
                               "value": best["videos_per_s"], "unit": "videos/s", "n_gpus": world, "steps": c4_steps, "warmup": 2,
@@ -585,7 +656,9 @@ def main():
         # the configs[2] leg on its own (what sub_results.config2_audio_visual_fusion runs), for profiling it alone
         if world != 1:
             raise SystemExit("--config 2 is the one-GPU audio + visual + fusion leg")
-        leg = config2_leg(extractor, scorer, dev, args.steps, args.videos or 50)
+        leg = config2_leg(extractor, scorer, dev, args.steps, args.videos or 50, outputs=dumped)
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps({"metric": "frames/sec end-to-end (extract+fuse+score), 224x224 + 16kHz", "value": leg["value"],
                           "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": 1,
                           "ms_per_step": leg["ms_per_step"], "higher_is_better": True, "scaling": "weak",
@@ -622,8 +695,11 @@ def main():
         torch.cuda.synchronize()
 
     elapsed, selected, prof = timed_steps(step, args.steps, args.warmup, barrier,
-                                          None if args.no_profile else args.profile_every)
+                                          args.profile_every if args.full and not args.no_profile else None)
     log(f"headline timed region {elapsed:.2f}s")
+    if dumped is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {"scores": last_scores[0].float().cpu().numpy(),
+                                         "selected_mask": selection_mask(selected, offsets)})
 
     t_all = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     n_all = torch.tensor([float(total)], dtype=torch.float64, device=dev)

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Generates the golden fixtures under tests/golden/ by IMPORTING the reference's own Python
-(/root/reference/models, features/fusion.py with a stub `fastdtw` module, utils, evaluation,
-scripts/evaluate.py) in this container and recording inputs + outputs.  Only data is written:
-no reference source text or bytecode.  Run:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+(<reference>/models, features/fusion.py with a stub `fastdtw` module, utils, evaluation,
+scripts/evaluate.py) and recording inputs + outputs.  Only data is written: no reference source text or bytecode.
+Run:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py <reference checkout> [--only reference_classes]
 """
+import argparse
 import hashlib
 import os
 import sys
@@ -13,7 +14,7 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
+REF = None   # the reference checkout, from the command line
 sys.dont_write_bytecode = True
 
 
@@ -37,7 +38,59 @@ def sd_hash(sd):
     return h.hexdigest()
 
 
+def reference_classes():
+    """reference_classes.npz: what tests/test_oracle_pins.py::test_against_reference_classes_directly compares the oracle
+    with - the reference classes' forward (three shapes) and parameter gradients of AVBiLSTMModel(32, 12, 16),
+    MultiHeadSelfAttention(48, 6), compute_dtw / interpolate_features, and both temporal-F1 functions."""
+    AVBiLSTMModel, MHSA, fusion, _, tf1 = ref_modules()
+    sys.path.insert(0, REF)
+    from utils.shot_metrics import compute_f1
+    sys.path.pop(0)
+    from oracle import fusion as ofu
+    out = {}
+    g = torch.Generator().manual_seed(77)
+    torch.manual_seed(3)
+    m = AVBiLSTMModel(32, 12, 16).eval()
+    out.update({"sd_" + k: v.numpy() for k, v in m.state_dict().items()})
+    for b, t in ((1, 50), (4, 9), (2, 1)):
+        v, a = torch.randn(b, t, 32, generator=g), torch.randn(b, t, 12, generator=g)
+        with torch.no_grad():
+            y = m(v, a)
+        out[f"fwd_{b}x{t}_visual"], out[f"fwd_{b}x{t}_audio"], out[f"fwd_{b}x{t}_out"] = v.numpy(), a.numpy(), y.numpy()
+    m.zero_grad()
+    vg, ag = torch.randn(1, 13, 32, generator=g), torch.randn(1, 13, 12, generator=g)
+    m(vg, ag).sum().backward()
+    out["bwd_visual"], out["bwd_audio"] = vg.numpy(), ag.numpy()
+    for k, p in m.named_parameters():
+        out["grad_" + k] = (p.grad if p.grad is not None else torch.zeros_like(p)).numpy()
+    at = MHSA(48, 6).eval()
+    x = torch.randn(3, 21, 48, generator=g)
+    with torch.no_grad():
+        out["mhsa_out"] = at(x).numpy()
+    out.update({"mhsa_sd_" + k: v.numpy() for k, v in at.state_dict().items()})
+    out["mhsa_x"] = x.numpy()
+    vv, aa = torch.randn(15, 8, generator=g), torch.randn(11, 8, generator=g)
+    cost = fusion.compute_dtw(vv, aa)
+    _, path = ofu.dtw_path(cost)
+    out.update(dtw_v=vv.numpy(), dtw_a=aa.numpy(), dtw_cost=cost, dtw_path=path,
+               interp=fusion.interpolate_features(vv, path, 9).numpy())
+    segs = ([(0, 10), (20, 30)], [(5, 15), (20, 25)])
+    out["temporal_f1"], out["shot_f1"] = tf1(*segs, 30), compute_f1(*segs, 30)
+    np.savez_compressed(os.path.join(HERE, "reference_classes.npz"), **out)
+
+
 def main():
+    global REF
+    ap = argparse.ArgumentParser()
+    ap.add_argument("reference", help="checkout of the reference (the directory holding models/, features/, utils/)")
+    ap.add_argument("--only", choices=["reference_classes"], default=None, help="write this one fixture only")
+    args = ap.parse_args()
+    REF = os.path.abspath(args.reference)
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))   # the repository root (oracle/)
+    if args.only == "reference_classes":
+        reference_classes()
+        print("golden fixture written to", HERE)
+        return
     AVBiLSTMModel, MHSA, fusion, align, tf1 = ref_modules()
     torch.manual_seed(1234)
     m = AVBiLSTMModel(64, 24, 32).eval()
@@ -103,6 +156,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "fusion_metrics.npz"), v=vv.numpy(), a=aa.numpy(), cost=cost, path=path,
                         interp=interp.numpy(), interp_dtype=str(interp.dtype), ann=ann, align=al.numpy(),
                         tf1=tf1([(0, 10), (20, 30)], [(5, 15), (20, 25)], 30))
+    reference_classes()
     print("golden fixtures written to", HERE)
 
 

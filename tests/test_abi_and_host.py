@@ -384,3 +384,29 @@ def test_stem_normalisation_folded_into_the_weights():
     got = F.conv2d(v4, w4, None, 2, 3)
     assert rows.view(64, 7, 8, 4)[:, :, 7].abs().max() == 0                            # the 8th pixel of a kernel row is padding
     assert (got - ref).abs().max().item() <= 2e-5 * ref.abs().max().item()            # (the folded rows are fp32)
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_cap(tmp_path):
+    """bench.py --dump-outputs: every array lands as <name>.npy unchanged while the total fits the cap; past it, one fixed
+    seeded sample of positions is taken from all arrays alike and written beside them.  The selection mask marks
+    exactly the selected frames of every video."""
+    import bench
+    scores = np.linspace(0.0, 1.0, 1000, dtype=np.float32)
+    mask = bench.selection_mask([np.array([0, 2]), np.array([1, 4])], [0, 3, 1000])
+    assert mask.dtype == np.float32 and np.flatnonzero(mask).tolist() == [0, 2, 4, 7]
+    assert bench.dump_outputs(str(tmp_path / "all"), {"scores": scores, "selected_mask": mask}) == ["scores", "selected_mask"]
+    assert np.array_equal(np.load(tmp_path / "all" / "scores.npy"), scores)
+    assert np.array_equal(np.load(tmp_path / "all" / "selected_mask.npy"), mask)
+    written = []
+    for run in range(2):
+        d = tmp_path / f"capped{run}"
+        names = bench.dump_outputs(str(d), {"scores": scores, "selected_mask": mask}, limit=4000)
+        assert names == ["sample_index", "scores", "selected_mask"]
+        assert sum(os.path.getsize(d / (n + ".npy")) - 128 for n in names) <= 4000      # 128-byte .npy headers
+        idx = np.load(d / "sample_index.npy")
+        assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+        assert np.array_equal(np.load(d / "scores.npy"), scores[idx.astype(np.int64)])
+        written.append(idx)
+    assert np.array_equal(written[0], written[1])
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "bad"), {"selected": np.arange(4)})

@@ -221,7 +221,7 @@ def test_bf16_batch_invariance(dev):
 
 
 def test_bench_contract_line(dev):
-    """bench.py on a tiny instance of configs[1]: exactly one JSON line on stdout with the fields the driver reads,
+    """bench.py --full on a tiny instance of configs[1]: exactly one JSON line on stdout with the fields the driver reads,
     the roofline measured live (HIP events) and the CPU-baseline leg."""
     import json
     import os
@@ -229,7 +229,7 @@ def test_bench_contract_line(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--videos", "2", "--mean-frames", "24",
-                          "--chunk", "16", "--steps", "1", "--warmup", "1", "--cpu-sample", "4"],
+                          "--chunk", "16", "--steps", "1", "--warmup", "1", "--cpu-sample", "4", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-800:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -257,6 +257,41 @@ def test_bench_contract_line(dev):
     assert d["sub_results"] is None                                     # only with the default headline
 
 
+def test_bench_plain_run_and_dump_outputs(dev, tmp_path):
+    """A plain bench.py run (no --full) on a tiny instance of configs[1]: the headline fields and nothing measured beside
+    them; --dump-outputs writes the last timed step's scores and selection, and a second run with the same arguments
+    writes the same arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from avsum_amd import synthetic
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        out_dir = str(tmp_path / f"run{run}")
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--videos", "2", "--mean-frames",
+                              "24", "--chunk", "16", "--steps", "2", "--warmup", "1", "--dump-outputs", out_dir],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-800:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f16x2" and d["value"] > 0
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert abs(d["value"] - d["config"]["frames_per_gpu"] * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["accuracy"] is None and d["sub_results"] is None
+        assert sorted(os.listdir(out_dir)) == ["scores.npy", "selected_mask.npy"]
+        dumps.append({k: np.load(os.path.join(out_dir, k + ".npy")) for k in ("scores", "selected_mask")})
+    offsets = synthetic.offsets_of(synthetic.config(1, 0, 1, 2, 24)["lengths"])
+    scores, mask = dumps[0]["scores"], dumps[0]["selected_mask"]
+    assert scores.dtype == np.float32 and mask.dtype == np.float32 and scores.shape == mask.shape == (offsets[-1],)
+    assert np.isfinite(scores).all()
+    for a, b in zip(offsets[:-1], offsets[1:]):                  # the selection rule of scripts/evaluate.py:26, per video
+        assert np.array_equal(mask[a:b], (scores[a:b] > scores[a:b].mean()).astype(np.float32))
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
 @pytest.mark.parametrize("dtype,config", [("f32split", "1"), ("f32", "1"), ("bf16", "1"), ("f16x2", "3")])
 def test_bench_other_headlines(dev, dtype, config):
     """The non-default headlines of bench.py stay runnable: the fp32 parity / fp32-split arithmetic modes (whose
@@ -268,7 +303,7 @@ def test_bench_other_headlines(dev, dtype, config):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", config, "--dtype", dtype, "--videos", "2",
                           "--mean-frames", "24", "--chunk", "16", "--steps", "1", "--warmup", "1", "--cpu-sample", "0",
-                          "--sub", "none"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--sub", "none", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-800:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1

@@ -1,9 +1,7 @@
-"""Pins the oracle (CPU restatement) against (a) the golden fixtures generated from the reference's own
-classes by tests/golden/make_golden.py and (b), where /root/reference exists, those classes directly."""
+"""Pins the oracle (CPU restatement) against the golden fixtures generated from the reference's own classes and
+functions by tests/golden/make_golden.py."""
 import hashlib
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -12,7 +10,6 @@ import torch
 from oracle import fusion as ofu, scorer as osc, selection as osel
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF = "/root/reference"
 
 
 def _sd(z, prefix="sd_"):
@@ -107,71 +104,51 @@ def test_fusion_metrics_golden():
     assert abs(float(z["tf1"]) - 0.5714285665) < 1e-9  # SURVEY A.10 probe
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "models")), reason="reference tree not present")
 def test_against_reference_classes_directly():
-    saved = {k: sys.modules.pop(k) for k in list(sys.modules) if k.split(".")[0] in
-             ("models", "features", "utils", "evaluation", "scripts")}
-    sys.path.insert(0, REF)
-    sys.dont_write_bytecode = True
-    try:
-        sys.modules.setdefault("fastdtw", types.SimpleNamespace(fastdtw=None))
-        from models.av_model import AVBiLSTMModel
-        from models.attention import MultiHeadSelfAttention
-        from features import fusion as rfu
-        from utils.shot_metrics import compute_f1
-        from evaluation.metrics import compute_temporal_f1
-        g = torch.Generator().manual_seed(77)
-        torch.manual_seed(3)
-        m = AVBiLSTMModel(32, 12, 16).eval()
-        for b, t in ((1, 50), (4, 9), (2, 1)):
-            v, a = torch.randn(b, t, 32, generator=g), torch.randn(b, t, 12, generator=g)
-            with torch.no_grad():
-                ref = m(v, a)
-            out = osc.av_bilstm_forward(m.state_dict(), v, a)
-            assert out.shape == ref.shape and (out - ref).abs().max().item() < 1e-6
-        # backward: torch autograd through the restatement == autograd through the reference module
-        m.zero_grad()
-        vg, ag = torch.randn(1, 13, 32, generator=g), torch.randn(1, 13, 12, generator=g)
-        m(vg, ag).sum().backward()
-        sd = {k: p.detach().clone().requires_grad_(True) for k, p in m.named_parameters()}
-        ones = torch.ones(13, 16)
-        grads = torch.autograd.grad(osc.av_bilstm_forward_train(sd, vg, ag, ones, ones).sum(), list(sd.values()),
-                                    allow_unused=True)
-        for (k, p), gr in zip(m.named_parameters(), grads):
-            want = p.grad if p.grad is not None else torch.zeros_like(p)
-            got = gr if gr is not None else torch.zeros_like(p)
-            assert (got - want).abs().max().item() < 1e-6, k
-        at = MultiHeadSelfAttention(48, 6).eval()
-        x = torch.randn(3, 21, 48, generator=g)
-        with torch.no_grad():
-            assert (osc.mhsa_forward(at.state_dict(), x, 6) - at(x)).abs().max().item() < 1e-6
-        vv, aa = torch.randn(15, 8, generator=g), torch.randn(11, 8, generator=g)
-        assert np.array_equal(ofu.compute_dtw(vv, aa), rfu.compute_dtw(vv, aa))
-        _, path = ofu.dtw_path(ofu.compute_dtw(vv, aa))
-        assert torch.equal(ofu.interpolate_features(vv, path, 9), rfu.interpolate_features(vv, path, 9))
-        segs = ([(0, 10), (20, 30)], [(5, 15), (20, 25)])
-        assert osel.compute_temporal_f1(*segs, 30) == compute_temporal_f1(*segs, 30) == compute_f1(*segs, 30)
-        # the metric block of scripts/evaluate.py:21-42 (its model loop needs .cuda(); restated lines only)
-        rng = np.random.default_rng(0)
-        preds = [rng.random(40).astype(np.float32) for _ in range(3)]
-        tgts = [rng.random(40).astype(np.float32) for _ in range(3)]
-        from scipy.stats import kendalltau, spearmanr
-        f1 = []
-        for p, t in zip(preds, tgts):
-            bp, bt = (p > np.mean(p)).astype(int), (t > np.mean(t)).astype(int)
-            tp = np.logical_and(bp, bt).sum()
-            pr, rc = tp / bp.sum(), tp / bt.sum()
-            f1.append(2 * (pr * rc) / (pr + rc + 1e-8))
-        got = osel.evaluate_metrics(preds, tgts)
-        assert got["f1"] == np.mean(f1)
-        assert got["spearman"] == np.mean([spearmanr(p, t).correlation for p, t in zip(preds, tgts)])
-        assert got["kendall"] == np.mean([kendalltau(p, t).correlation for p, t in zip(preds, tgts)])
-    finally:
-        sys.path.remove(REF)
-        for k in list(sys.modules):
-            if k.split(".")[0] in ("models", "features", "utils", "evaluation", "scripts"):
-                del sys.modules[k]
-        sys.modules.update(saved)
+    """The oracle against what the reference's classes and functions computed when they were run directly
+    (tests/golden/make_golden.py imports them and stores their inputs, parameters and outputs: reference_classes.npz)."""
+    z = np.load(os.path.join(GOLD, "reference_classes.npz"))
+    sd = _sd(z)
+    for b, t in ((1, 50), (4, 9), (2, 1)):
+        v, a = torch.from_numpy(z[f"fwd_{b}x{t}_visual"]), torch.from_numpy(z[f"fwd_{b}x{t}_audio"])
+        ref = torch.from_numpy(z[f"fwd_{b}x{t}_out"])
+        out = osc.av_bilstm_forward(sd, v, a)
+        assert out.shape == ref.shape and (out - ref).abs().max().item() < 1e-6
+    # backward: torch autograd through the restatement == autograd through the reference module
+    vg, ag = torch.from_numpy(z["bwd_visual"]), torch.from_numpy(z["bwd_audio"])
+    params = {k: p.clone().requires_grad_(True) for k, p in sd.items()}
+    ones = torch.ones(13, 16)
+    grads = torch.autograd.grad(osc.av_bilstm_forward_train(params, vg, ag, ones, ones).sum(), list(params.values()),
+                                allow_unused=True)
+    assert sorted(params) == sorted(k[len("grad_"):] for k in z.files if k.startswith("grad_"))
+    for (k, p), gr in zip(params.items(), grads):
+        want = torch.from_numpy(z["grad_" + k])
+        got = gr if gr is not None else torch.zeros_like(p)
+        assert (got - want).abs().max().item() < 1e-6, k
+    x = torch.from_numpy(z["mhsa_x"])
+    assert (osc.mhsa_forward(_sd(z, "mhsa_sd_"), x, 6) - torch.from_numpy(z["mhsa_out"])).abs().max().item() < 1e-6
+    vv, aa = torch.from_numpy(z["dtw_v"]), torch.from_numpy(z["dtw_a"])
+    assert np.array_equal(ofu.compute_dtw(vv, aa), z["dtw_cost"])
+    _, path = ofu.dtw_path(ofu.compute_dtw(vv, aa))
+    assert np.array_equal(np.asarray(path), z["dtw_path"])
+    assert torch.equal(ofu.interpolate_features(vv, path, 9), torch.from_numpy(z["interp"]))
+    segs = ([(0, 10), (20, 30)], [(5, 15), (20, 25)])
+    assert osel.compute_temporal_f1(*segs, 30) == float(z["temporal_f1"]) == float(z["shot_f1"])
+    # the metric block of scripts/evaluate.py:21-42 (its model loop needs .cuda(); restated lines only)
+    rng = np.random.default_rng(0)
+    preds = [rng.random(40).astype(np.float32) for _ in range(3)]
+    tgts = [rng.random(40).astype(np.float32) for _ in range(3)]
+    from scipy.stats import kendalltau, spearmanr
+    f1 = []
+    for p, t in zip(preds, tgts):
+        bp, bt = (p > np.mean(p)).astype(int), (t > np.mean(t)).astype(int)
+        tp = np.logical_and(bp, bt).sum()
+        pr, rc = tp / bp.sum(), tp / bt.sum()
+        f1.append(2 * (pr * rc) / (pr + rc + 1e-8))
+    got = osel.evaluate_metrics(preds, tgts)
+    assert got["f1"] == np.mean(f1)
+    assert got["spearman"] == np.mean([spearmanr(p, t).correlation for p, t in zip(preds, tgts)])
+    assert got["kendall"] == np.mean([kendalltau(p, t).correlation for p, t in zip(preds, tgts)])
 
 
 def test_dtw_path_is_optimal_bruteforce():

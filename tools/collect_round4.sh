@@ -13,4 +13,4 @@ run() {   # name, bench flags...
 run train --config 4 --steps 10 && run both --steps 2 --extractor resnet50+inception3 && run config2 --config 2 --steps 1 &&
 run fpg1 --steps 2 --frames-per-group 1 && run bf16 --steps 2 --dtype bf16
 cd $R && python tools/inception_layer_table.py > $O/${TAG}_inception_layer_table.txt 2>&1
-python bench.py > $O/${TAG}_bench_full.json 2> $O/${TAG}_bench_full.log; grep "sub-result\|headline\|cross" $O/${TAG}_bench_full.log
+python bench.py --full > $O/${TAG}_bench_full.json 2> $O/${TAG}_bench_full.log; grep "sub-result\|headline\|cross" $O/${TAG}_bench_full.log
