@@ -17,6 +17,7 @@ log without the spectrum ever leaving the chip.  ``spectrum`` keeps the unfused
 dense-DFT kernel (the form VGGish's 512-point front end uses) for tests.
 """
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -83,6 +84,16 @@ def folded_dft_tables():
     n = np.arange(1, N_FFT // 2)[:, None]
     sin_t[:N_FFT // 2 - 1, :N_BINS] = -np.sin(2.0 * math.pi * ((k * n) % N_FFT) / N_FFT)
     return cos_t, sin_t
+
+
+SHOT_MIN = 960   # features/extractors.py:207-208: a shot shorter than this is zero padded to it
+
+# MelPlan.shot_tables: the batch's tracks in one buffer + per-shot tables of the mel front end and of VGGish (device tensors)
+#   waves fp32 [>= 4, a multiple of 4]   track_off / track_len int64 [ntracks]   shots int64 [nshot, 3] = (track, first
+#   sample inside the track, present length)   blocks int32 [nblocks, 3] = (first frame inside the shot, frames <= 32, shot)
+#   seg_block int32 [nshot + 1]   seg_frames int32 [nshot]   ex_start int64 [nex] = first sample of each VGGish example in
+#   waves   ex_seg int64 [nshot + 1] = first example of each shot
+ShotTables = namedtuple("ShotTables", "waves track_off track_len shots blocks seg_block seg_frames ex_start ex_seg")
 
 
 class _SegmentTable(tuple):
@@ -217,6 +228,58 @@ class MelPlan:
         cat, toff, tlen, blocks, seg_block, seg_frames = tables
         return ops.stft_mel_segmean_batch(cat, toff, tlen, self.window, self.cos_t, self.sin_t, self.fb, self.fb_lo, self.fb_hi,
                                           blocks, seg_block, seg_frames, top_db=top_db, out_log2=out_log2, out_db=out_mfcc_db)[:2]
+
+    @staticmethod
+    def shot_tables(waves, bounds_per_track, device):
+        """Per-shot tables for shot_means_batch and VGGish.embed_shots: waves = the tracks (1-D numpy / torch, any float
+        dtype; stored as float32, 16-byte aligned starts), bounds_per_track = per track the host sample bounds [(s0, s1),
+        ...] of its shots.  Python slice semantics (track[s0:s1]): s1 is clipped to the track, s1 <= s0 gives an empty
+        shot, negative bounds count from the end.  A shot of L samples is its own signal of Lp = max(L, 960) samples
+        (zero tail): 1 + Lp // 200 STFT frames in blocks of at most 32, VGGishFrontEnd.num_examples(Lp) examples; an
+        empty shot has neither.  Works on any device (device="cpu" builds the tables without a GPU)."""
+        from .vggish import EXAMPLE_FRAMES, HOP as VGG_HOP, VGGishFrontEnd
+        waves = [w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w)) for w in waves]
+        if len(waves) != len(bounds_per_track):
+            raise ValueError("shot_tables: one list of bounds per track")
+        offs, lens, cur = [], [], 0
+        for w in waves:
+            if w.dim() != 1:
+                raise ValueError("shot_tables: tracks must be 1-D")
+            offs.append(cur)
+            lens.append(int(w.numel()))
+            cur += (int(w.numel()) + 3) // 4 * 4
+        cat = torch.zeros(max(cur, 4), dtype=torch.float32, device=device)
+        for w, o in zip(waves, offs):
+            cat[o:o + w.numel()] = w.to(device=device, dtype=torch.float32)
+        shots, blocks, seg_block, seg_frames, ex_start, ex_seg = [], [], [0], [], [], [0]
+        for trk, (bounds, ln) in enumerate(zip(bounds_per_track, lens)):
+            for s0, s1 in bounds:
+                a, b, _ = slice(int(s0), int(s1)).indices(ln)
+                n = max(0, b - a)
+                sh = len(shots)
+                shots.append((trk, a, n))
+                nf = 1 + max(n, SHOT_MIN) // HOP if n > 0 else 0
+                for f in range(0, nf, 32):
+                    blocks.append((f, min(32, nf - f), sh))
+                seg_block.append(len(blocks))
+                seg_frames.append(nf)
+                nex = VGGishFrontEnd.num_examples(max(n, SHOT_MIN)) if n > 0 else 0
+                ex_start.extend(offs[trk] + a + e * EXAMPLE_FRAMES * VGG_HOP for e in range(nex))
+                ex_seg.append(len(ex_start))
+        mk = lambda v, shape, dt: torch.tensor(v, dtype=dt).reshape(shape).to(device)
+        return ShotTables(cat, mk(offs, (len(offs),), torch.int64), mk(lens, (len(lens),), torch.int64),
+                          mk(shots, (len(shots), 3), torch.int64), mk(blocks, (len(blocks), 3), torch.int32),
+                          mk(seg_block, (len(seg_block),), torch.int32), mk(seg_frames, (len(seg_frames),), torch.int32),
+                          mk(ex_start, (len(ex_start),), torch.int64), mk(ex_seg, (len(ex_seg),), torch.int64))
+
+    def shot_means_batch(self, tables, out_log2=None, out_db=None, top_db=80.0):
+        """Per shot (tables = shot_tables(...)), each shot its own signal: the time mean of the log2-mel rows (out_log2
+        [nshot, >= n_mels]) and of the dB-mel rows clamped at the SHOT's maximum - top_db (out_db; its DCT is the mean of
+        the MFCC rows) - what features/extractors.py:195-234 compute on waveform[s0:s1], for every shot of every track in
+        one set of launches (avs_stft_mel_shots_f32)."""
+        return ops.stft_mel_shots(tables.waves, tables.track_off, tables.track_len, tables.shots, self.window, self.cos_t,
+                                  self.sin_t, self.fb, self.fb_lo, self.fb_hi, tables.blocks, tables.seg_block,
+                                  tables.seg_frames, top_db=top_db, out_log2=out_log2, out_db=out_db)[:2]
 
     def segment_means(self, wave, table, out_log2=None, out_mfcc_db=None, top_db=80.0):
         """Per segment (a shot's slice of the track) the time mean of the log2-mel rows (out_log2 [nseg, >= n_mels]) and

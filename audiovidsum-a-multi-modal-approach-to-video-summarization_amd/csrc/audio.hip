@@ -46,22 +46,37 @@ extern "C" int avs_reflect_pad_f32(const float* d_x, int64_t t, int pad, float* 
 // ---------------------------------------------------------------------------
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
+// EX: frame rows come from a table of examples - row r is frame r % ex_frames of the example starting at sample
+// ex_start[r / ex_frames] of x (x_len samples), each sample clamped to [-1, 1] at load - instead of r * hop.
+template <bool EX>
 __global__ __launch_bounds__(256) void stft_f64_kernel(const float* __restrict__ xpad, long long frames, int hop,
                                                        int nfft, const double* __restrict__ basis_t, int ncols,
-                                                       int ncols_pad, float* __restrict__ spec) {
+                                                       int ncols_pad, float* __restrict__ spec,
+                                                       const long long* __restrict__ ex_start, int ex_frames,
+                                                       long long x_len) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int lr = lane & 15, lq = lane >> 4;
   const long long r0 = (long long)blockIdx.x * 64 + wave * 16;
   const int c0 = blockIdx.y * 64;
   const long long fr = r0 + lr;
   const bool row_ok = fr < frames;
-  const float* __restrict__ xrow = xpad + (row_ok ? fr : 0) * hop;
+  const float* __restrict__ xrow;
+  if constexpr (EX) {
+    const long long e = (row_ok ? fr : 0) / ex_frames;
+    const long long last = x_len - ((long long)(ex_frames - 1) * hop + nfft);   // the last start whose frames fit in x
+    long long st = ex_start[e];
+    st = st < 0 ? 0 : (st > last ? last : st);   // (the table is device data: never read past x)
+    xrow = xpad + st + ((row_ok ? fr : 0) - e * ex_frames) * hop;
+  } else {
+    xrow = xpad + (row_ok ? fr : 0) * hop;
+  }
   f64x4 acc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) acc[i] = (f64x4){0.0, 0.0, 0.0, 0.0};
   for (int k0 = 0; k0 < nfft; k0 += 4) {
     const int k = k0 + lq;
-    const double a = (row_ok && k < nfft) ? (double)xrow[k] : 0.0;
+    double a = 0.0;
+    if (row_ok && k < nfft) a = EX ? (double)fminf(fmaxf(xrow[k], -1.f), 1.f) : (double)xrow[k];
     const double* __restrict__ brow = basis_t + (long long)(k < nfft ? k : 0) * ncols_pad + c0 + lr;
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
@@ -93,8 +108,8 @@ extern "C" int avs_stft_f64(const float* d_xpad, int64_t xpad_len, int64_t frame
               nfft, hop, (long long)xpad_len);
   const long long bx = avs_cdiv(frames, 64);
   AVS_REQUIRE(bx < (1ll << 31), AVS_E_SHAPE, "avs_stft_f64: too many frames");
-  hipLaunchKernelGGL(stft_f64_kernel, dim3((unsigned)bx, ncols_pad / 64), dim3(256), 0, (hipStream_t)stream, d_xpad,
-                     (long long)frames, hop, nfft, d_basis_t, ncols, ncols_pad, d_spec);
+  hipLaunchKernelGGL(stft_f64_kernel<false>, dim3((unsigned)bx, ncols_pad / 64), dim3(256), 0, (hipStream_t)stream, d_xpad,
+                     (long long)frames, hop, nfft, d_basis_t, ncols, ncols_pad, d_spec, (const long long*)nullptr, 1, 0ll);
   AVS_CHECK_LAUNCH("avs_stft_f64");
   return AVS_OK;
 }
@@ -189,23 +204,48 @@ extern "C" int avs_power_mel_f32(const float* d_spec, int64_t frames, int nbins,
 // 10 log10(*max_in) - top_db) go to part_log2 / part_db [block, nmel]; segment_fold_kernel adds a segment's blocks in
 // block order and divides by its frame count - the time means of a shot (features/extractors.py:232-246 take means over
 // time of the per-frame matrices) without the [frames, nmel] matrices ever reaching HBM.  Deterministic.
-template <bool SEG>
+//
+// SHOT (with SEG): every block row (first STFT frame inside the shot, frames <= 32, shot) names a SHOT, its own signal:
+// shots[s] = (track, first sample inside the track, present length L); the signal is the L samples at x + track_off[track]
+// + first, zero padded to Lp = max(L, 960), clamped to [-1, 1] (at load: clamp is elementwise) and reflect padded at ITS
+// first and last sample; 1 + Lp / 200 frames; its maximum goes to gmax[s] (features/extractors.py:195-234 on the slice).
+template <bool SEG, bool SHOT = false>
 __global__ __launch_bounds__(256, 2) void stft_mel_fused_kernel(
     const float* __restrict__ x, long long t, long long frames, const double* __restrict__ window,
     const double* __restrict__ cos_t, const double* __restrict__ sin_t, const float* __restrict__ fb,
     const int* __restrict__ fb_lo, const int* __restrict__ fb_hi, int nmel, float* __restrict__ out_log2,
     float* __restrict__ out_db, float* __restrict__ out_pow, float* __restrict__ gmax, const int* __restrict__ blocks,
     float* __restrict__ part_log2, float* __restrict__ part_db, const float* __restrict__ max_in, float top_db,
-    float* __restrict__ db_rows, const long long* __restrict__ track_off, const long long* __restrict__ track_len) {
+    float* __restrict__ db_rows, const long long* __restrict__ track_off, const long long* __restrict__ track_len,
+    const long long* __restrict__ shots, int nshot, int ntracks, long long x_len) {
   // SEG batch mode (track_off != nullptr): block rows are (first frame, frames, segment, track); the block's waveform is
   // x + track_off[track] (track_len[track] samples), its maximum gmax[track] - every track of a batch in ONE launch
-  const int bstride = (SEG && track_off) ? 4 : 3;
-  if (SEG && track_off) {
+  const int bstride = (SEG && track_off && !SHOT) ? 4 : 3;
+  if (SEG && track_off && !SHOT) {
     const int trk = blocks[4 * blockIdx.x + 3];
     x += track_off[trk];
     t = track_len[trk];
     frames = 1 + t / AVS_FUSED_HOP;
     if (gmax) gmax += trk;
+  }
+  long long sbase = 0, slen = 0;   // SHOT: index of the shot's first sample in x, its present length L
+  if constexpr (SHOT) {
+    // (the tables are device data: every index is clamped so that no load leaves x[0, x_len))
+    int s = blocks[3 * blockIdx.x + 2];
+    s = s < 0 ? 0 : (s >= nshot ? nshot - 1 : s);
+    int trk = (int)shots[3 * s];
+    trk = trk < 0 ? 0 : (trk >= ntracks ? ntracks - 1 : trk);
+    long long toff = track_off[trk], tlen = track_len[trk];
+    toff = toff < 0 ? 0 : (toff > x_len ? x_len : toff);
+    tlen = tlen < 0 ? 0 : (tlen > x_len - toff ? x_len - toff : tlen);
+    long long first = shots[3 * s + 1];
+    first = first < 0 ? 0 : (first > tlen ? tlen : first);
+    slen = shots[3 * s + 2];
+    slen = slen < 0 ? 0 : (slen > tlen - first ? tlen - first : slen);
+    sbase = toff + first;
+    t = slen > 960 ? slen : 960;   // Lp
+    frames = 1 + t / AVS_FUSED_HOP;
+    if (gmax) gmax += s;
   }
   constexpr int SPAN = AVS_FUSED_FPB * AVS_FUSED_HOP + (AVS_FUSED_NFFT - AVS_FUSED_HOP);   // 6600 samples
   __shared__ __attribute__((aligned(16))) float span[SPAN];
@@ -216,6 +256,40 @@ __global__ __launch_bounds__(256, 2) void stft_mel_fused_kernel(
   if (SEG) f0 = f0 < 0 ? 0 : (f0 >= frames ? frames - 1 : f0);   // device table: clamped into the track
   // ---- stage the span: padded position q = f0 * 200 + i is sample q - 200, reflected at both ends
   const long long q0 = f0 * AVS_FUSED_HOP - AVS_FUSED_NFFT / 2;
+  if constexpr (SHOT) {
+    // the shot starts at any sample: x + sbase + j is 16-byte aligned when sh = (sbase + q0) mod 4 (the same for every
+    // thread: q0 and i are multiples of 4) is 0; otherwise two aligned 16-byte loads and a shift.  x_len is a multiple
+    // of 4, so the aligned quads around a sample of the track stay inside x.  Samples L .. Lp - 1 read as zero.
+    const int sh = (int)((sbase + q0) & 3);
+    for (int i = tid * 4; i < SPAN; i += 256 * 4) {
+      const long long j = q0 + i;
+      float4 v;
+      if (j >= 0 && j + 3 < slen) {
+        const float4* p = reinterpret_cast<const float4*>(x + (sbase + j - sh));
+        const float4 lo = p[0];
+        if (sh == 0) {
+          v = lo;
+        } else {
+          const float4 hi = p[1];
+          v = sh == 1 ? make_float4(lo.y, lo.z, lo.w, hi.x)
+                      : (sh == 2 ? make_float4(lo.z, lo.w, hi.x, hi.y) : make_float4(lo.w, hi.x, hi.y, hi.z));
+        }
+        v = make_float4(fminf(fmaxf(v.x, -1.f), 1.f), fminf(fmaxf(v.y, -1.f), 1.f), fminf(fmaxf(v.z, -1.f), 1.f),
+                        fminf(fmaxf(v.w, -1.f), 1.f));
+      } else {
+        float e[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          long long jj = j + u;
+          if (jj < 0) jj = -jj;
+          if (jj >= t) jj = 2 * (t - 1) - jj;
+          e[u] = (jj >= 0 && jj < slen) ? fminf(fmaxf(x[sbase + jj], -1.f), 1.f) : 0.f;   // zero tail; past the last window
+        }
+        v = make_float4(e[0], e[1], e[2], e[3]);
+      }
+      *reinterpret_cast<float4*>(span + i) = v;
+    }
+  } else
   for (int i = tid * 4; i < SPAN; i += 256 * 4) {
     const long long j = q0 + i;
     float4 v;
@@ -360,19 +434,20 @@ extern "C" int avs_stft_mel_fused_f32(const float* d_wave, int64_t t, const doub
   hipLaunchKernelGGL(stft_mel_fused_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_wave,
                      (long long)t, frames, d_window, d_cos, d_sin, d_fb, d_fb_lo, d_fb_hi, nmel, d_log2mel, d_db, d_power,
                      d_max, (const int*)nullptr, (float*)nullptr, (float*)nullptr, (const float*)nullptr, 0.f, (float*)nullptr,
-                     (const long long*)nullptr, (const long long*)nullptr);
+                     (const long long*)nullptr, (const long long*)nullptr, (const long long*)nullptr, 0, 0, 0ll);
   AVS_CHECK_LAUNCH(who);
   return AVS_OK;
 }
 
 // One-pass mode of avs_stft_mel_segmean_f32: part_db[b, m] = sum over the block's frames (in order) of max(db_rows, threshold),
 // the threshold from the track maximum the front-end pass has just found.  Bandwidth-bound: reads the dB rows once.
+// max_col: the column of the block row that picks the block's maximum (-1: one maximum for all blocks).
 __global__ __launch_bounds__(256) void segment_db_sum_kernel(const float* __restrict__ db_rows, const int* __restrict__ blocks,
-                                                             int bstride, int nmel, const float* __restrict__ gmax,
+                                                             int bstride, int max_col, int nmel, const float* __restrict__ gmax,
                                                              float top_db, float* __restrict__ part_db) {
   int nf = blocks[bstride * blockIdx.x + 1];
   nf = nf < 0 ? 0 : (nf > AVS_FUSED_FPB ? AVS_FUSED_FPB : nf);
-  if (bstride == 4) gmax += blocks[4 * blockIdx.x + 3];   // batch mode: the block's track
+  if (max_col >= 0) gmax += blocks[bstride * blockIdx.x + max_col];   // batch mode: the block's track; shot mode: its shot
   const float thr = 10.f * log10f(*gmax) - top_db;
   for (int m = threadIdx.x; m < nmel; m += 256) {
     const float* __restrict__ r = db_rows + (long long)blockIdx.x * AVS_FUSED_FPB * nmel + m;
@@ -434,9 +509,9 @@ extern "C" int avs_stft_mel_segmean_f32(const float* d_wave, int64_t t, const do
     hipLaunchKernelGGL(stft_mel_fused_kernel<true>, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, d_wave,
                        (long long)t, frames, d_window, d_cos, d_sin, d_fb, d_fb_lo, d_fb_hi, nmel, (float*)nullptr,
                        (float*)nullptr, (float*)nullptr, one_pass ? d_max : (float*)nullptr, d_blocks, p_log2, p_db, d_max,
-                       top_db, rows, (const long long*)nullptr, (const long long*)nullptr);
+                       top_db, rows, (const long long*)nullptr, (const long long*)nullptr, (const long long*)nullptr, 0, 0, 0ll);
     if (one_pass)
-      hipLaunchKernelGGL(segment_db_sum_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, rows, d_blocks, 3, nmel,
+      hipLaunchKernelGGL(segment_db_sum_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, rows, d_blocks, 3, -1, nmel,
                          d_max, top_db, p_db);
   }
   long long gx = avs_cdiv((long long)nseg * nmel, 256);
@@ -482,9 +557,9 @@ extern "C" int avs_stft_mel_segmean_batch_f32(const float* d_waves, const int64_
     hipLaunchKernelGGL(stft_mel_fused_kernel<true>, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, d_waves, 0ll, 0ll,
                        d_window, d_cos, d_sin, d_fb, d_fb_lo, d_fb_hi, nmel, (float*)nullptr, (float*)nullptr, (float*)nullptr,
                        d_mean_db ? d_max : (float*)nullptr, d_blocks, p_log2, p_db, d_max, top_db, rows,
-                       (const long long*)d_track_off, (const long long*)d_track_len);
+                       (const long long*)d_track_off, (const long long*)d_track_len, (const long long*)nullptr, 0, 0, 0ll);
     if (d_mean_db)
-      hipLaunchKernelGGL(segment_db_sum_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, rows, d_blocks, 4, nmel,
+      hipLaunchKernelGGL(segment_db_sum_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, rows, d_blocks, 4, 3, nmel,
                          d_max, top_db, p_db);
   }
   long long gx = avs_cdiv((long long)nseg * nmel, 256);
@@ -495,6 +570,101 @@ extern "C" int avs_stft_mel_segmean_batch_f32(const float* d_waves, const int64_
   if (d_mean_db)
     hipLaunchKernelGGL(segment_fold_kernel, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, p_db, d_seg_block,
                        d_seg_frames, nseg, nmel, d_mean_db, (long long)ld_db);
+  AVS_CHECK_LAUNCH(who);
+  return AVS_OK;
+}
+
+// PER-SHOT means for the shots of a batch of tracks, each shot its own signal (see SHOT above): d_shots int64 [nshot, 3] =
+// (track, first sample inside the track, present length L), d_blocks int32 [nblocks, 3] = (first STFT frame inside the
+// shot, frames <= 32, shot), d_max fp32 [nshot] receives every shot's maximum.  Same launches as the batch form.
+extern "C" int64_t avs_stft_mel_shots_workspace_bytes(int nblocks, int nmel, int want_log2, int want_db) {
+  return avs_stft_mel_segmean_workspace_bytes(nblocks, nmel, want_log2, want_db, 1);
+}
+
+extern "C" int avs_stft_mel_shots_f32(const float* d_waves, int64_t waves_len, const int64_t* d_track_off,
+                                      const int64_t* d_track_len, int ntracks, const int64_t* d_shots, int nshot,
+                                      const double* d_window, const double* d_cos, const double* d_sin, const float* d_fb,
+                                      const int* d_fb_lo, const int* d_fb_hi, int nmel, const int* d_blocks, int nblocks,
+                                      const int* d_seg_block, const int* d_seg_frames, float* d_max, float top_db,
+                                      float* d_mean_log2, int64_t ld_log2, float* d_mean_db, int64_t ld_db, void* d_ws,
+                                      int64_t ws_bytes, avs_stream_t stream) {
+  const char* who = "avs_stft_mel_shots_f32";
+  AVS_REQUIRE(waves_len >= 0 && waves_len % 4 == 0 && ntracks >= 0 && nshot >= 0 && nmel > 0 && nmel <= 1024 && nblocks >= 0,
+              AVS_E_SHAPE, "%s: waves_len=%lld (a multiple of 4) ntracks=%d nshot=%d nmel=%d nblocks=%d", who,
+              (long long)waves_len, ntracks, nshot, nmel, nblocks);
+  AVS_REQUIRE(nblocks == 0 || (ntracks > 0 && nshot > 0 && waves_len > 0), AVS_E_SHAPE, "%s: %d blocks but no shots or tracks",
+              who, nblocks);
+  if (nshot == 0) return AVS_OK;
+  AVS_REQUIRE(d_window && d_cos && d_sin && d_fb && d_fb_lo && d_fb_hi && d_seg_block && d_seg_frames && d_max &&
+                  (nblocks == 0 || (d_waves && d_track_off && d_track_len && d_shots && d_blocks)),
+              AVS_E_ARG, "%s: null pointer", who);
+  AVS_REQUIRE(d_mean_log2 || d_mean_db, AVS_E_ARG, "%s: no output requested", who);
+  AVS_REQUIRE((!d_mean_log2 || ld_log2 >= nmel) && (!d_mean_db || ld_db >= nmel), AVS_E_SHAPE, "%s: output rows too short", who);
+  AVS_REQUIRE(avs_aligned16(d_waves), AVS_E_ALIGN, "%s: the waveforms must be 16-byte aligned", who);
+  const int64_t per = (int64_t)nblocks * nmel * 4;
+  const int64_t need = avs_stft_mel_shots_workspace_bytes(nblocks, nmel, d_mean_log2 != nullptr, d_mean_db != nullptr);
+  AVS_REQUIRE(d_ws && ws_bytes >= need, AVS_E_WORKSPACE, "%s: workspace %lld < %lld bytes", who, (long long)ws_bytes, (long long)need);
+  float* p_log2 = d_mean_log2 ? (float*)d_ws : nullptr;
+  float* p_db = d_mean_db ? (float*)((char*)d_ws + (d_mean_log2 ? per : 0)) : nullptr;
+  float* rows = d_mean_db ? (float*)((char*)d_ws + per * ((d_mean_log2 ? 1 : 0) + 1)) : nullptr;
+  AVS_REQUIRE(hipMemsetAsync(d_max, 0, sizeof(float) * nshot, (hipStream_t)stream) == hipSuccess, AVS_E_HIP, "%s: memset", who);
+  if (nblocks > 0) {
+    hipLaunchKernelGGL((stft_mel_fused_kernel<true, true>), dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, d_waves,
+                       0ll, 0ll, d_window, d_cos, d_sin, d_fb, d_fb_lo, d_fb_hi, nmel, (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr, d_mean_db ? d_max : (float*)nullptr, d_blocks, p_log2, p_db, d_max, top_db, rows,
+                       (const long long*)d_track_off, (const long long*)d_track_len, (const long long*)d_shots, nshot, ntracks,
+                       (long long)waves_len);
+    if (d_mean_db)
+      hipLaunchKernelGGL(segment_db_sum_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, rows, d_blocks, 3, 2,
+                         nmel, d_max, top_db, p_db);
+  }
+  long long gx = avs_cdiv((long long)nshot * nmel, 256);
+  if (gx > 4096) gx = 4096;
+  if (d_mean_log2)
+    hipLaunchKernelGGL(segment_fold_kernel, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, p_log2, d_seg_block,
+                       d_seg_frames, nshot, nmel, d_mean_log2, (long long)ld_log2);
+  if (d_mean_db)
+    hipLaunchKernelGGL(segment_fold_kernel, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, p_db, d_seg_block,
+                       d_seg_frames, nshot, nmel, d_mean_db, (long long)ld_db);
+  AVS_CHECK_LAUNCH(who);
+  return AVS_OK;
+}
+
+// VGGish log-mel examples of a ragged batch: example e is 96 frames (window 400, hop 160, no padding) starting at sample
+// d_ex_start[e] of d_waves, samples clamped to [-1, 1] at load.  The same two kernels and the same per-frame arithmetic as
+// avs_stft_f64 + avs_power_mel_f32 mode 3 on a clamped slice (fp64 DFT, fp32 spectrum through the workspace).
+#define AVS_VGG_WINDOW 400
+#define AVS_VGG_HOP 160
+#define AVS_VGG_BINS 257
+#define AVS_VGG_FRAMES 96
+extern "C" int64_t avs_vggish_examples_workspace_bytes(int64_t nex) {
+  if (nex < 0) return AVS_E_SHAPE;
+  return nex * AVS_VGG_FRAMES * 2 * AVS_VGG_BINS * 4;   // the fp32 spectrum rows [nex * 96, 514]
+}
+
+extern "C" int avs_vggish_examples_f32(const float* d_waves, int64_t waves_len, const int64_t* d_ex_start, int64_t nex,
+                                       const double* d_basis_t, int ncols_pad, const float* d_fb, const int* d_fb_lo,
+                                       const int* d_fb_hi, int nmel, float* d_out, void* d_ws, int64_t ws_bytes,
+                                       avs_stream_t stream) {
+  const char* who = "avs_vggish_examples_f32";
+  const long long ex_len = (long long)(AVS_VGG_FRAMES - 1) * AVS_VGG_HOP + AVS_VGG_WINDOW;   // 15 600 samples
+  AVS_REQUIRE(nex >= 0 && waves_len >= 0 && nmel > 0 && ncols_pad >= 2 * AVS_VGG_BINS && ncols_pad % 64 == 0, AVS_E_SHAPE,
+              "%s: nex=%lld waves_len=%lld nmel=%d ncols_pad=%d", who, (long long)nex, (long long)waves_len, nmel, ncols_pad);
+  if (nex == 0) return AVS_OK;
+  AVS_REQUIRE(waves_len >= ex_len, AVS_E_SHAPE, "%s: an example needs %lld samples, the buffer has %lld", who, ex_len,
+              (long long)waves_len);
+  AVS_REQUIRE(d_waves && d_ex_start && d_basis_t && d_fb && d_fb_lo && d_fb_hi && d_out, AVS_E_ARG, "%s: null pointer", who);
+  const int64_t need = avs_vggish_examples_workspace_bytes(nex);
+  AVS_REQUIRE(d_ws && ws_bytes >= need, AVS_E_WORKSPACE, "%s: workspace %lld < %lld bytes", who, (long long)ws_bytes, (long long)need);
+  const long long frames = nex * AVS_VGG_FRAMES;
+  const long long bx = avs_cdiv(frames, 64), bm = avs_cdiv(frames, AVS_MEL_FPB);
+  AVS_REQUIRE(bx < (1ll << 31) && bm < (1ll << 31), AVS_E_SHAPE, "%s: too many examples", who);
+  float* spec = (float*)d_ws;
+  hipLaunchKernelGGL(stft_f64_kernel<true>, dim3((unsigned)bx, ncols_pad / 64), dim3(256), 0, (hipStream_t)stream, d_waves,
+                     frames, AVS_VGG_HOP, AVS_VGG_WINDOW, d_basis_t, 2 * AVS_VGG_BINS, ncols_pad, spec,
+                     (const long long*)d_ex_start, AVS_VGG_FRAMES, (long long)waves_len);
+  hipLaunchKernelGGL(power_mel_kernel, dim3((unsigned)bm), dim3(256), (size_t)AVS_MEL_FPB * AVS_VGG_BINS * sizeof(float),
+                     (hipStream_t)stream, spec, frames, AVS_VGG_BINS, d_fb, d_fb_lo, d_fb_hi, nmel, 3, d_out, (float*)nullptr);
   AVS_CHECK_LAUNCH(who);
   return AVS_OK;
 }

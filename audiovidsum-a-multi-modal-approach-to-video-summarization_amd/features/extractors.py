@@ -161,6 +161,33 @@ class AudioFeatureExtractor(nn.Module):
             out[168:] = ops.segment_mean(vg.contiguous(), seg_v)[0].cpu().numpy()   # vggish_feats.mean(0), :234
         return out
 
+    def forward_shots(self, waveform, bounds):
+        """np [S, 296] = np.array([self(waveform[a:b]) for a, b in bounds]) (row for row and in dtype, within fp32
+        rounding), every shot its own signal, in one set of launches with no host round trip (forward_shots_batch)."""
+        return self.forward_shots_batch([waveform], [bounds])
+
+    def forward_shots_batch(self, waveforms, bounds_per_track):
+        """The rows of forward_shots for every track of a batch, concatenated in track order: one set of launches for all
+        shots of all tracks.  Intent mode: [mean MFCC (40) | mean log2-mel (128) | mean VGGish (128)] per shot, each shot
+        the clamped, zero-padded-to-960 slice forward sees (audio.MelPlan.shot_tables: Python slice semantics); strict
+        mode: forward's literal zeros, no GPU work."""
+        if self.strict_reference:
+            return np.array([self(np.asarray(w)[a:b]) for w, bounds in zip(waveforms, bounds_per_track) for a, b in bounds])
+        nshot = sum(len(b) for b in bounds_per_track)
+        if nshot == 0:
+            return np.array([])   # what np.array of an empty list of rows is
+        dev = _device()
+        plan = MelPlan.get(self.sr, 128, 40, dev)
+        tables = plan.shot_tables([np.asarray(w) if not isinstance(w, torch.Tensor) else w for w in waveforms],
+                                  bounds_per_track, dev)
+        out = torch.empty((nshot, 296), dtype=torch.float32, device=dev)
+        mean_db = torch.empty((nshot, 128), dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            plan.shot_means_batch(tables, out[:, 40:168], mean_db)
+            ops.linear(mean_db, plan.dct, out=out[:, :40])    # the DCT of the mean dB row IS the mean MFCC row (linear)
+            self.vggish.embed_shots(tables, out[:, 168:])
+        return out.cpu().numpy()
+
     def _extract_mfcc(self, waveform):
         """extractors.py:236-239: MFCC(sr, n_mfcc=40) -> permute -> mfcc_proj -> np [time,128]."""
         wave = torch.as_tensor(waveform).float().to(_device())
@@ -231,18 +258,26 @@ class AVProcessor:
         from .shots import detect_shots
         return detect_shots(np.stack([_as_bgr_u8(f) for f in frames]))
 
-    def process_decoded(self, frames, waveform, fps, shots=None):
+    def process_decoded(self, frames, waveform, fps, shots=None, batch_audio=False):
         """The per-shot loop of process_video (extractors.py:344-362) on already-decoded input:
         frames = indexable of uint8 HxWx3 for the whole video, waveform = mono float array at self.sr,
-        shots = [(start_frame, end_frame)] or None to run the shot detector on the frames."""
+        shots = [(start_frame, end_frame)] or None to run the shot detector on the frames.
+        batch_audio=True: the audio rows of all shots come from ONE AudioFeatureExtractor.forward_shots call (the same
+        per-shot values within fp32 rounding) instead of one extractor call per shot."""
         if shots is None:
             shots = self._detect_shots_decoded(frames)
         visual, audio = [], []
+        bounds = []
         for start, end in shots:
             picked = [frames[i] for i in sample_shot_indices(start, min(end, len(frames)))]
             visual.append(self.visual_extractor(picked))
             s0, s1 = int(start / fps * self.sr), int(end / fps * self.sr)
-            audio.append(self.audio_extractor(waveform[s0:s1]))
+            if batch_audio:
+                bounds.append((s0, s1))
+            else:
+                audio.append(self.audio_extractor(waveform[s0:s1]))
+        if batch_audio:
+            return np.array(visual), self.audio_extractor.forward_shots(waveform, bounds)
         return np.array(visual), np.array(audio)
 
     def process_video(self, video_path):

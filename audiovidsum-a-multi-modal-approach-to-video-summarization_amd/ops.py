@@ -14,7 +14,7 @@ from ._abi import (ACT_NONE, ACT_RELU, AVS_BF16, AVS_F16X2, AVS_F32, AVS_F32_SPL
 __all__ = [
     "ACT_NONE", "ACT_RELU", "linear", "gemm_nt_batched", "conv2d", "conv2d_raw", "conv2d_split", "conv_bnlocal_tile_rows", "conv_bncluster_ok", "cluster_exchange_errors", "lstm_split_errors", "conv1x1_bn", "conv1x1_gram_bn", "bn_gram_affine", "gram_supported", "frames_normalize", "pull_copy", "stem_conv_bn_pool", "stem_h2_operands", "stem_conv_pool_h2", "resize_bilinear",
     "bn_batch_stats", "bn_apply", "bn_maxpool", "pool2d", "global_avgpool", "segment_mean", "hsv_frame_diff", "reflect_pad", "stft_f64", "stft_mel_fused", "power_mel",
-    "clamp_topdb", "stft_mel_max", "stft_mel_segmean", "stft_mel_segmean_batch", "fill", "quantize", "resample", "lstm", "mha_batchaxis", "score_head", "mhsa_flash", "softmax_rows", "cdist", "dtw_path",
+    "clamp_topdb", "stft_mel_max", "stft_mel_segmean", "stft_mel_segmean_batch", "stft_mel_shots", "vggish_examples", "fill", "quantize", "resample", "lstm", "mha_batchaxis", "score_head", "mhsa_flash", "softmax_rows", "cdist", "dtw_path",
     "gather_scale", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
 ]
 
@@ -1041,6 +1041,62 @@ def stft_mel_segmean_batch(waves, track_off, track_len, window, cos_t, sin_t, fb
                                              out_db.stride(0) if out_db is not None else 0, _p(ws), ws.numel(), _stream()),
         "avs_stft_mel_segmean_batch_f32"))
     return out_log2, out_db, gmax
+
+
+def stft_mel_shots(waves, track_off, track_len, shots, window, cos_t, sin_t, fb, fb_lo, fb_hi, blocks, seg_block, seg_frames,
+                   top_db=80.0, out_log2=None, out_db=None):
+    """Per-shot time means, each shot its own signal (avs_stft_mel_shots_f32): waves = the tracks one after another (fp32,
+    16-byte aligned starts, length a multiple of 4), track_off / track_len int64 [ntracks], shots int64 [nshot, 3] = (track,
+    first sample inside the track, present length), blocks int32 [nblocks, 3] = (first frame inside the shot, frames <= 32,
+    shot), seg_block int32 [nshot + 1], seg_frames int32 [nshot] - all on the device (audio.MelPlan.shot_tables builds
+    them).  Returns (out_log2, out_db, gmax[nshot]): gmax is each shot's own maximum the top_db clamp was relative to."""
+    _dev(waves, track_off, track_len, shots, blocks, seg_block, seg_frames, out_log2, out_db)
+    _f32(waves, "waves")
+    nmel = fb.shape[1]
+    ntracks, nshot, nblocks = track_len.numel(), seg_frames.numel(), blocks.shape[0]
+    gmax = torch.empty(max(nshot, 1), dtype=torch.float32, device=waves.device)
+    need = int(lib().avs_stft_mel_shots_workspace_bytes(nblocks, nmel, int(out_log2 is not None), int(out_db is not None)))
+    key = _ws_key(waves.device)
+    ws = _segmean_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=waves.device)
+        _segmean_ws[key] = ws
+    nbytes = 4.0 * waves.numel() + 4.0 * nshot * nmel * (int(out_log2 is not None) + int(out_db is not None))
+    _timed("audio", AVS_F32, nbytes, lambda: check(
+        lib().avs_stft_mel_shots_f32(_p(waves), waves.numel(), _p(track_off), _p(track_len), ntracks, _p(shots), nshot,
+                                     _p(window), _p(cos_t), _p(sin_t), _p(fb), _p(fb_lo), _p(fb_hi), nmel, _p(blocks), nblocks,
+                                     _p(seg_block), _p(seg_frames), _p(gmax), float(top_db), _p(out_log2),
+                                     out_log2.stride(0) if out_log2 is not None else 0, _p(out_db),
+                                     out_db.stride(0) if out_db is not None else 0, _p(ws), ws.numel(), _stream()),
+        "avs_stft_mel_shots_f32"))
+    return out_log2, out_db, gmax
+
+
+_vggish_ws = {}
+
+
+def vggish_examples(waves, ex_start, basis_t, fb, fb_lo, fb_hi):
+    """VGGish log-mel examples of a ragged batch (avs_vggish_examples_f32): ex_start int64 [nex] = first sample of each
+    example in waves (fp32, clamped to [-1, 1] at load) -> fp32 [nex, 96, n_mels], the values stft_f64 + power_mel mode 3
+    give for the clamped samples."""
+    _dev(waves, ex_start, basis_t, fb)
+    _f32(waves, "waves")
+    if basis_t.dtype != torch.float64 or not basis_t.is_contiguous() or basis_t.shape[0] != 400:
+        raise ValueError("basis_t must be contiguous float64 [400, ncols_pad]")
+    nex, nmel = ex_start.numel(), fb.shape[1]
+    out = torch.empty((nex, 96, nmel), dtype=torch.float32, device=waves.device)
+    if nex == 0:
+        return out
+    need = int(lib().avs_vggish_examples_workspace_bytes(nex))
+    key = _ws_key(waves.device)
+    ws = _vggish_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=waves.device)
+        _vggish_ws[key] = ws
+    check(lib().avs_vggish_examples_f32(_p(waves), waves.numel(), _p(ex_start), nex, _p(basis_t), basis_t.shape[1], _p(fb),
+                                        _p(fb_lo), _p(fb_hi), nmel, _p(out), _p(ws), ws.numel(), _stream()),
+          "avs_vggish_examples_f32")
+    return out
 
 
 def clamp_topdb(x, gmax, top_db):

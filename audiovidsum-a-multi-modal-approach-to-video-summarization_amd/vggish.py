@@ -187,6 +187,25 @@ class VGGish(nn.Module):
         return ops.quantize(ops.linear(emb.contiguous(), e, b), QUANT_MIN, QUANT_MAX, 255.0 / (QUANT_MAX - QUANT_MIN))
 
     @torch.no_grad()
+    def embed_shots(self, tables, out=None):
+        """tables = audio.MelPlan.shot_tables(...) on the device -> fp32 [nshot, 128] (or into `out`, rows of unit column
+        stride): per shot the mean over its examples of what forward(clamped shot) returns (post-processed when
+        self.postprocess), zeros for a shot without examples.  The examples of all shots come from one
+        avs_vggish_examples_f32 call, then one embed_examples and one post."""
+        nshot = tables.ex_seg.numel() - 1
+        dev = tables.waves.device
+        if out is None:
+            out = torch.empty((nshot, 128), dtype=torch.float32, device=dev)
+        if tables.ex_start.numel() == 0 or nshot == 0:
+            return out.zero_()
+        fe = VGGishFrontEnd.get(dev)
+        examples = ops.vggish_examples(tables.waves, tables.ex_start, fe.basis_t, fe.fb, fe.fb_lo, fe.fb_hi)
+        emb = self.embed_examples(examples)
+        if self.postprocess:
+            emb = self.post(emb)
+        return ops.segment_mean(emb.contiguous(), tables.ex_seg, out)
+
+    @torch.no_grad()
     def forward(self, x, fs=None):
         if not torch.cuda.is_available():
             raise RuntimeError("avsum_amd needs an MI355X (HIP device); there is no CPU fallback")

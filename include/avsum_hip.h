@@ -491,6 +491,40 @@ int avs_stft_mel_segmean_batch_f32(const float* d_waves, const int64_t* d_track_
                                    float* d_mean_log2, int64_t ld_log2, float* d_mean_db, int64_t ld_db, void* d_ws,
                                    int64_t ws_bytes, avs_stream_t stream);
 
+/* PER-SHOT time means for the shots of a batch of tracks, each shot its own signal (features/extractors.py:351-356 slice
+ * the waveform and :195-234 run the extractor on the slice): d_waves fp32 [waves_len] holds the tracks one after another
+ * (16-byte aligned; track i at sample offset d_track_off[i], a multiple of 4, d_track_len[i] samples; waves_len a
+ * multiple of 4), d_shots int64 [nshot, 3] = (track, first sample inside the track - any offset -, present length L after
+ * clipping to the track).  Shot s is the signal x = clamp(pad(slice, Lp), -1, 1) with Lp = max(L, 960) (samples L .. Lp-1
+ * zero), reflect padded by 200 at ITS first and last sample: 1 + Lp / 200 STFT frames, read in place (no per-shot copy).
+ * d_blocks int32 [nblocks, 3] = (first STFT frame inside the shot, frames <= 32, shot) - every shot cut into runs of at
+ * most 32 frames -, d_seg_block int32 [nshot + 1] = first block of each shot, d_seg_frames int32 [nshot] = its frames.
+ * Out: d_mean_log2 [nshot, ld_log2] = time mean of log2(mel + 1e-6), d_mean_db [nshot, ld_db] = time mean of the dB mel
+ * clamped at 10 log10(d_max[s]) - top_db, d_max fp32 [nshot] = each shot's OWN largest clamped mel power (find_max = 1
+ * semantics per shot: one pass of the DFT writes the unclamped dB rows to the workspace, a bandwidth-bound pass clamps
+ * and sums them).  Shots are independent: they may overlap, be unsorted or be empty; an empty shot (L = 0) has no blocks
+ * and no launch work and its rows are zero.  Index fields are clamped on the device so that no load leaves the buffer.
+ * d_ws: avs_stft_mel_shots_workspace_bytes(...) bytes; deterministic (block partial sums folded in order).              */
+int64_t avs_stft_mel_shots_workspace_bytes(int nblocks, int nmel, int want_log2, int want_db);
+int avs_stft_mel_shots_f32(const float* d_waves, int64_t waves_len, const int64_t* d_track_off, const int64_t* d_track_len,
+                           int ntracks, const int64_t* d_shots, int nshot, const double* d_window, const double* d_cos,
+                           const double* d_sin, const float* d_fb, const int* d_fb_lo, const int* d_fb_hi, int nmel,
+                           const int* d_blocks, int nblocks, const int* d_seg_block, const int* d_seg_frames, float* d_max,
+                           float top_db, float* d_mean_log2, int64_t ld_log2, float* d_mean_db, int64_t ld_db, void* d_ws,
+                           int64_t ws_bytes, avs_stream_t stream);
+
+/* VGGish log-mel examples of a ragged batch (vggish_input.waveform_to_examples per shot): example e = 96 frames of 400
+ * samples at hop 160 (no padding) starting at sample d_ex_start[e] (int64 [nex]) of d_waves (waves_len samples; a start
+ * is clamped on the device into [0, waves_len - 15600]), each sample clamped to [-1, 1] at load.  d_out fp32 [nex, 96,
+ * nmel] = ln(|STFT| . mel + 0.01); d_basis_t as avs_stft_f64 ([400, ncols_pad] float64, 257 re | 257 im columns),
+ * d_fb [257, nmel] as avs_power_mel_f32.  Two launches (the fp64 DFT into the workspace, then avs_power_mel_f32 mode 3's
+ * kernel): the per-frame arithmetic of avs_stft_f64 + avs_power_mel_f32 mode 3, so the examples are bit-identical to those
+ * of a clamped slice.  d_ws: avs_vggish_examples_workspace_bytes(nex) bytes.  nex = 0: no launch.                      */
+int64_t avs_vggish_examples_workspace_bytes(int64_t nex);
+int avs_vggish_examples_f32(const float* d_waves, int64_t waves_len, const int64_t* d_ex_start, int64_t nex,
+                            const double* d_basis_t, int ncols_pad, const float* d_fb, const int* d_fb_lo, const int* d_fb_hi,
+                            int nmel, float* d_out, void* d_ws, int64_t ws_bytes, avs_stream_t stream);
+
 /* Power spectrum -> mel filterbank -> log.  d_spec is [frames, 2*nbins]
  * (re | im per frame, from avs_gemm_nt against the windowed DFT basis);
  * d_fb is [nbins, nmel] (torchaudio melscale_fbanks layout).
