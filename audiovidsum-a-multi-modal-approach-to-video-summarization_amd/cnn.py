@@ -145,6 +145,8 @@ class ResNet50Runner:
                                      # one-pass form on ONE Gram matrix of the stem output): no finishing pass
         self.defer_bn_apply = True   # bn2 + ReLU applied inside conv3's two-pass kernel (avs_conv1x1_bn_in_bf16)
         self.defer_res_apply = True  # the downsample's BatchNorm applied inside conv3's residual add (layer 2's first block)
+        self.fold_input_bn = True    # AVS_F16X2: conv1 of the stride-1 bottlenecks stays RAW and its bn1 + ReLU ride in the
+                                     # staging of conv2's nine-tap kernel (avs_conv2d_nhwc_bnstats_xin): no apply pass over it
         self.gram_finish_min_k = 128  # >= this many input channels: the Gram kernel stores the finished input in place, so
                                       # the convolution pass (N / 128 column slabs) does not transform it per slab
         self.affine_variant = 0      # tile override of the one-pass 1x1 form (study: _abi.TILE_128 / TILE_256)
@@ -272,7 +274,7 @@ class ResNet50Runner:
                 and cout >= 2 * cin and gmax >= self.fuse_min_rows)
 
     def _conv_bn(self, geom, xs, x, wt, bnp, groups, residual=None, relu=True, local=False, algo_k=None, pool=None,
-                 defer=False, in_affine=None, res_affine=None, out_p8=False):
+                 defer=False, in_affine=None, res_affine=None, out_p8=False, x_affine=None):
         """One convolution + BatchNorm (+ residual, + ReLU) -> NHWC activation; picks the form (class docstring).
         pool = (k, s, p): a max pooling follows (the stem) - on the split form it is fused with the BatchNorm apply
         (avs_bn_maxpool_nhwc: the normalised full-resolution map is never written).
@@ -281,7 +283,10 @@ class ResNet50Runner:
         res_affine: the residual is a deferred (raw) downsample output; its BatchNorm rides in this layer's residual add
         (one-pass 1x1 form only).
         out_p8: the output as an AVS_F16P8 tensor (ops.P8; the one-pass 1x1 form only - the caller has checked that the
-        layer takes it); x / residual may be P8 tensors where the forms that read them take that format."""
+        layer takes it); x / residual may be P8 tensors where the forms that read them take that format.
+        x_affine = (scale, shift): x is the RAW output of the layer before (its `defer` result); its BatchNorm + ReLU are
+        applied inside this layer's nine-tap convolution + statistics kernel where the library takes the shape, else by an
+        apply pass over x in place first (the same values either way)."""
         n, ho, wo, cout = geom[0], geom[10], geom[11], geom[12]
         cin, kh, sh = geom[3], geom[4], geom[6]
         dev, dt = x.device, self.dtype
@@ -320,10 +325,18 @@ class ResNet50Runner:
             return finish(scale.view(1, -1), shift.view(1, -1), None, 0)
         grows, gmax, uniform = groups[ho * wo]
         bf16 = dt == torch.bfloat16
+
+        def apply_x():
+            xg = groups[geom[1] * geom[2]]
+            ops.bn_apply(x.view(-1, cin), x_affine[0], x_affine[1], xg[0], xg[1], None, ops.ACT_RELU, x.view(-1, cin),
+                         code=self.ecode)
         # statistics from the convolution's epilogue: the bf16 mode, and the fp32-split mode (whose products already carry
         # ~2^-15 of error: the E[y^2] - E[y]^2 form on fp32 sums costs nothing next to that); the exact fp32 parity mode
         # keeps the shifted statistics pass over the stored output
         fast = uniform and (bf16 or self.f32_split or self.h2)
+        if x_affine is not None and not (fast and self.h2 and not local and in_affine is None and kh == 3):
+            apply_x()   # only the AVS_F16X2 convolution + statistics form takes a raw input
+            x_affine = None
         if fast and (bf16 or self.h2) and local:
             cluster = local if (local is not True and int(local) > 1) else 1   # (the plan: True = one group per tile)
             conv(act=act, bnlocal=(gmax, gamma, beta, eps, residual), cluster=cluster)
@@ -359,7 +372,13 @@ class ResNet50Runner:
         if fast:
             # statistics from the convolution's epilogue: per-tile partial sums of the fp32 accumulators, folded in
             # tile order (E[x^2]-E[x]^2: fine for bf16 activations); None = groups too small for that form
-            affine = conv(bnstats=(gmax, gamma, beta, eps))
+            if x_affine is not None:
+                affine = conv(bnstats=(gmax, gamma, beta, eps), x_affine=(x_affine[0], x_affine[1], True))
+                if affine is None:   # (not the nine-tap form: the apply pass, then the plain one)
+                    apply_x()
+                x_affine = None
+            if affine is None:
+                affine = conv(bnstats=(gmax, gamma, beta, eps))
         if affine is None and isinstance(x, ops.P8):
             raise RuntimeError("an AVS_F16P8 input belongs to the convolution + statistics form")
         if affine is None:
@@ -438,6 +457,7 @@ class ResNet50Runner:
             sd = slot() if "cd" in blk else False
             s3 = slot()
             idn = None
+            aff1 = None   # (scale, shift) of bn1 when t1 is conv1's RAW output
             if x_aff is not None and self.h2:
                 # AVS_F16X2, first block on the fused stem's RAW pooled map: the Gram pass applies bn1 + ReLU on the way in,
                 # stores the finished activation in place (the identity input of nothing else: conv1 and the downsample
@@ -490,8 +510,14 @@ class ResNet50Runner:
                                   idn, planes * 4, gmax, sc[:, c1n:].contiguous(), sf[:, c1n:].contiguous(), None, False,
                                   None, w_layout=layout)
             else:
+                # fold_input_bn: conv1's output stays raw, its bn1 + ReLU applied by conv2 (which falls back to the apply
+                # pass where its shape does not take the nine-tap form)
+                fold1 = (self.fold_input_bn and self.h2 and self.bn_mode == "batch" and uniform and s == 1
+                         and not s1 and not s2)
                 geom, xs, _ = self._nhwc_geom(n, hcur, cin, 1, 1, 0, planes)
-                t1 = self._conv_bn(geom, xs, x, blk["c1"], blk["b1"], groups, local=s1)
+                t1 = self._conv_bn(geom, xs, x, blk["c1"], blk["b1"], groups, local=s1, defer=fold1)
+                if isinstance(t1, tuple):
+                    t1, aff1 = t1
             # bn2 + ReLU ride in conv3's input staging when conv3 takes the two-pass kernel: conv2 then only
             # writes its raw output and statistics (no apply pass over it)
             gmax3 = gsz * hout * hout
@@ -499,7 +525,7 @@ class ResNet50Runner:
                       ((dt == torch.bfloat16 and planes <= 512 and self._twopass_ok(planes, planes * 4, 1, 1, gmax3))
                        or self._gram_h2_ok(planes, planes * 4, 1, 1, gmax3)))
             geom, xs, _ = self._nhwc_geom(n, hcur, planes, 3, s, 1, planes)
-            t2 = self._conv_bn(geom, xs, t1, blk["c2"], blk["b2"], groups, local=s2, defer=defer2)
+            t2 = self._conv_bn(geom, xs, t1, blk["c2"], blk["b2"], groups, local=s2, defer=defer2, x_affine=aff1)
             aff2 = None
             if defer2:
                 t2, aff2 = t2

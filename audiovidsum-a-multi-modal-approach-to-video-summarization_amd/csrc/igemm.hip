@@ -124,8 +124,14 @@ __device__ __forceinline__ void avs_split_bf16(const float4& p0, const float4& p
 // fetched the A fragments straight into registers - a wave owns its 64 rows for all columns on these tiles, nothing is
 // shared - with buffer_load_dwordx4 + dwordx2 per lane: 19 - 25 % SLOWER than the AVS_F16X2 path, 16-byte pieces of 32
 // rows per instruction; removed.)
+// XIN (TAP9, AVS_F16X2 convolution + statistics): the input is a RAW activation with its BatchNorm affine given per group
+// (p.in_scale / p.in_shift, + ReLU when p.in_relu).  When a 16-channel block has landed in LDS, the workgroup rewrites it
+// once - join hi + lo, v * scale + shift (a multiply and an add, as avs_bn_apply), ReLU, split - behind one extra barrier,
+// and the nine taps read the finished values: the apply pass over the input (a read and a write of it in HBM) disappears.
+// The zero rows the padding taps read stay zero (the padding belongs to the finished activation), so the products, the
+// outputs and the statistics are those of avs_bn_apply followed by the plain form, bit for bit.
 template <int ES, int BN, bool ACC64, bool SPATIAL, int ROWB, int EPI, bool PIPE, int WR = 2, bool FASTK = false,
-          int SPLIT = 0, bool TAP9 = false, bool AP8 = false>
+          int SPLIT = 0, bool TAP9 = false, bool AP8 = false, bool XIN = false>
 __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64 && ES == 2) ? 4 : 3) : 2) void igemm_kernel(
     IgemmParams p) {
   static_assert(!AP8 || (SPLIT == 2 && ES == 4 && PIPE && ROWB == 64 && FASTK && !SPATIAL && !TAP9 && EPI == EPI_STATS),
@@ -134,6 +140,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
                           SPATIAL && (EPI == EPI_STATS || EPI == EPI_BNLOCAL || (EPI == EPI_BRELU && SPLIT == 2))),
                 "the shifted-row form: AVS_F16X2 / bf16 convolution + statistics / tile-local BatchNorm (3x3), AVS_F16X2 bias + "
                 "ReLU (any stride-1 'same' filter) on the pipelined 256-row tiles");
+  static_assert(!XIN || (TAP9 && SPLIT == 2 && EPI == EPI_STATS), "the input affine: AVS_F16X2 nine-tap convolution + statistics");
   static_assert(SPLIT == 0 || (ES == 4 && !ACC64), "the split arithmetic is for 4-byte operands");
   static_assert(WR == 2 || (WR == 4 && !ACC64 && (ES == 2 || SPLIT != 0)),
                 "256-row tiles are built for the bf16 variants and the fp32-split arithmetic");
@@ -503,6 +510,38 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         ++sb_blk;
       }
     };
+    // XIN: block b's 384 buffer rows x 2 runs of 8 channels (hi chunk + lo chunk), three (row, run) pairs per thread; the
+    // rows outside the input (zeros, never read by a tap inside a frame) are left alone
+    auto xin_block = [&](int b) {
+      uint4* ab = lds + (b & 1) * T9_ABUF;
+#pragma unroll
+      for (int i = 0; i < (T9_AROWS * 2) / 256; ++i) {
+        const int u = t + 256 * i;
+        const int a = u >> 1, run = u & 1;
+        const int m = m0 - w1 + a;
+        if (m < 0 || m >= p.M) continue;
+        const int g = m / p.rows_per_group;
+        const long long ch = (long long)g * p.cin + b * BKE + run * 8;
+        uint4& hi = ab[a * CPRR + ((2 * run) ^ ((a >> SH) & (CPRR - 1)))];
+        uint4& lo = ab[a * CPRR + ((2 * run + 1) ^ ((a >> SH) & (CPRR - 1)))];
+        float v[8], sc[8], sf[8];
+        avs_f16x2_join8(hi, lo, v);
+        *reinterpret_cast<float4*>(&sc[0]) = *reinterpret_cast<const float4*>(p.in_scale + ch);
+        *reinterpret_cast<float4*>(&sc[4]) = *reinterpret_cast<const float4*>(p.in_scale + ch + 4);
+        *reinterpret_cast<float4*>(&sf[0]) = *reinterpret_cast<const float4*>(p.in_shift + ch);
+        *reinterpret_cast<float4*>(&sf[4]) = *reinterpret_cast<const float4*>(p.in_shift + ch + 4);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[j] + sf[j];
+        if (p.in_relu) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
+        }
+        uint4 h, l;
+        avs_f16x2_split8(v, h, l);
+        hi = h;
+        lo = l;
+      }
+    };
     stage_a(0, 0);
     stage_b();
     if (steps > 1) stage_b();
@@ -520,6 +559,13 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       __builtin_amdgcn_s_barrier();
+      if constexpr (XIN) {
+        if (tap == 0) {   // block blk has landed (every wave's share: the barrier above); no tap has read it yet
+          xin_block(blk);
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_s_barrier();
+        }
+      }
       const unsigned abuf = lds_base + (unsigned)(blk & 1) * (T9_ABUF * 16u);
       const unsigned bbase = lds_base + (unsigned)(2 * T9_ABUF + slot * T9_BBUF) * 16u;
       uint4 fa[2][2], fb[2][NT];
@@ -1682,6 +1728,13 @@ static bool igemm_taps_ok(const IgemmParams& p) {
   } while (0)
 template <int ES, int BN, bool ACC64, bool SP, int ROWB, bool PIPE, int WR, bool FK>
 static bool igemm_dispatch_epi4(int epi, dim3 grid, hipStream_t stream, const IgemmParams& p) {
+  if (p.in_scale) {   // the input-affine form exists as the AVS_F16X2 nine-tap convolution + statistics only
+    if constexpr (ES == 4 && !ACC64 && SP && ROWB == 64 && PIPE && WR == 4 && FK) {
+      if (p.split == 2 && epi == EPI_STATS && igemm_tap9_ok(p, ES))
+        AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_STATS, PIPE, WR, FK, 2, true, false, true>));
+    }
+    return false;
+  }
   if constexpr (ES == 2 && WR == 4) {
     if constexpr (SP && ROWB == 64 && PIPE && FK) {   // bf16 3x3 / 1 layers: the nine-tap form
       if ((epi == EPI_BNLOCAL || epi == EPI_STATS) && igemm_tap9_ok(p, ES)) {
@@ -2179,11 +2232,10 @@ extern "C" int64_t avs_conv2d_bnstats_workspace_bytes(const avs_conv_desc* d, in
   return st == AVS_OK ? ws : (int64_t)st;
 }
 
-extern "C" int avs_conv2d_nhwc_bnstats(const avs_conv_desc* d, const void* d_x, const void* d_w, void* d_y,
-                                       int64_t rows_per_group, const float* d_gamma, const float* d_beta, float eps,
-                                       float* d_scale, float* d_shift, void* d_ws, int64_t ws_bytes,
-                                       avs_stream_t stream) {
-  const char* who = "avs_conv2d_nhwc_bnstats";
+static int conv_bnstats(const avs_conv_desc* d, const void* d_x, const void* d_w, void* d_y, int64_t rows_per_group,
+                        const float* d_gamma, const float* d_beta, float eps, float* d_scale, float* d_shift, void* d_ws,
+                        int64_t ws_bytes, const float* d_in_scale, const float* d_in_shift, int in_relu, avs_stream_t stream,
+                        const char* who) {
   IgemmParams p{};
   int st = conv_fill_params(d, d_x, d_w, nullptr, d_y, p, who);
   if (st != AVS_OK) return st;
@@ -2192,6 +2244,20 @@ extern "C" int avs_conv2d_nhwc_bnstats(const avs_conv_desc* d, const void* d_x, 
   int tile_rows = 0;
   st = bnstats_plan(d, rows_per_group, p, &need, &tile_rows, who);
   if (st != AVS_OK) return st;
+  if (d_in_scale || d_in_shift) {
+    // the kernel igemm_dispatch_epi4 would pick: the nine-tap form on the pipelined 256-row tiles with the scalar tap walk
+    IgemmParams q = p;
+    q.lin_stride = -1;
+    AVS_REQUIRE(d->dtype == AVS_F16X2 && tile_rows == 256 && g_pipe3 && igemm_tap9_ok(q, 4) &&
+                    igemm_fastk_ok(q, 4, 16, q.N <= 64 ? 64 : 128),
+                AVS_E_UNSUPPORTED, "%s: the input affine rides in the AVS_F16X2 nine-tap form only (3x3 / stride 1 / pad 1 on "
+                "a dense input at most 63 pixels wide, 256-row tiles)", who);
+    AVS_REQUIRE(d_in_scale && d_in_shift && avs_aligned16(d_in_scale) && avs_aligned16(d_in_shift), AVS_E_ARG,
+                "%s: in_scale / in_shift [groups, cin] must both be given, 16-byte aligned", who);
+    p.in_scale = d_in_scale;
+    p.in_shift = d_in_shift;
+    p.in_relu = in_relu ? 1 : 0;
+  }
   AVS_REQUIRE(d_gamma && d_beta && d_scale && d_shift && d_ws, AVS_E_ARG, "%s: null pointer", who);
   AVS_REQUIRE(ws_bytes >= need, AVS_E_WORKSPACE, "%s: workspace %lld < %lld bytes", who, (long long)ws_bytes,
               (long long)need);
@@ -2210,6 +2276,25 @@ extern "C" int avs_conv2d_nhwc_bnstats(const avs_conv_desc* d, const void* d_x, 
                      d_shift, d->dtype == AVS_F16X2 ? 1 : 0);
   AVS_CHECK_LAUNCH(who);
   return AVS_OK;
+}
+
+extern "C" int avs_conv2d_nhwc_bnstats(const avs_conv_desc* d, const void* d_x, const void* d_w, void* d_y,
+                                       int64_t rows_per_group, const float* d_gamma, const float* d_beta, float eps,
+                                       float* d_scale, float* d_shift, void* d_ws, int64_t ws_bytes,
+                                       avs_stream_t stream) {
+  return conv_bnstats(d, d_x, d_w, d_y, rows_per_group, d_gamma, d_beta, eps, d_scale, d_shift, d_ws, ws_bytes, nullptr,
+                      nullptr, 0, stream, "avs_conv2d_nhwc_bnstats");
+}
+
+extern "C" int avs_conv2d_nhwc_bnstats_xin(const avs_conv_desc* d, const void* d_x, const void* d_w, void* d_y,
+                                           int64_t rows_per_group, const float* d_gamma, const float* d_beta, float eps,
+                                           float* d_scale, float* d_shift, void* d_ws, int64_t ws_bytes,
+                                           const float* d_in_scale, const float* d_in_shift, int in_relu,
+                                           avs_stream_t stream) {
+  const char* who = "avs_conv2d_nhwc_bnstats_xin";
+  AVS_REQUIRE(d_in_scale && d_in_shift, AVS_E_ARG, "%s: in_scale / in_shift must be given", who);
+  return conv_bnstats(d, d_x, d_w, d_y, rows_per_group, d_gamma, d_beta, eps, d_scale, d_shift, d_ws, ws_bytes, d_in_scale,
+                      d_in_shift, in_relu, stream, who);
 }
 
 // ---- convolution + whole BatchNorm in one launch, statistics local to a tile (EPI_BNLOCAL) ----

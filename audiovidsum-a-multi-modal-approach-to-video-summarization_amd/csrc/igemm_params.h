@@ -60,6 +60,12 @@ struct IgemmParams {
   unsigned epoch;
   unsigned long long* xchg;
   unsigned* xerr;    // a counter of waves whose bounded wait ran out (0 = every exchange completed)
+  // input affine of the nine-tap convolution + statistics form (AVS_F16X2, avs_conv2d_nhwc_bnstats_xin): the input is a
+  // RAW activation whose BatchNorm (+ ReLU) is applied as each 16-channel block lands in LDS - x = act(x * in_scale[g] +
+  // in_shift[g]), g = row / rows_per_group, in_scale / in_shift [groups, cin]
+  const float* in_scale;
+  const float* in_shift;
+  int in_relu;
 #ifdef AVS_STUDY
   int debug;  // ablation switches of the kernel-study build (tools/): 1 = skip output stores, 2 = skip A/B loads, ...
 #endif

@@ -324,7 +324,7 @@ def _stats_workspace(device, nbytes):
 
 def conv2d_raw(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x, x_img_stride, x_row_stride, x_px_stride,
                wt, w_row_stride, y, y_px_stride, bias=None, act=ACT_NONE, alpha=1.0, x_off=0, y_off=0, algo_k=None,
-               bnstats=None, bnlocal=None, algo_in_elems=None, w_layout=0, variant=0, cluster=1):
+               bnstats=None, bnlocal=None, algo_in_elems=None, w_layout=0, variant=0, cluster=1, x_affine=None):
     """algo_k: the algorithmic reduction length when it differs from kh*kw*cin (zero-padded stem rows);
     algo_in_elems: input elements the launch reads when the geometry does not say (the re-viewed stem image).
     bnstats = (rows_per_group, gamma, beta, eps): the BatchNorm batch statistics of equal-sized row groups from the
@@ -335,7 +335,10 @@ def conv2d_raw(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x, x_i
     cluster > 1 (with bnlocal): a group = `cluster` tiles (avs_conv2d_nhwc_bncluster: AVS_F16X2, 14x14 maps).
     w_layout: _abi.AVS_W_ROWS (wt[cout, K]) or AVS_W_KSTEP32 (the image weights_kstep32() makes).
     variant: avs_conv_desc.variant (_abi.TILE_128 / TILE_256 | STAGING_GENERIC): a per-call override of the tile /
-    staging choice, for tests and the study tools (the library has no global tuning state)."""
+    staging choice, for tests and the study tools (the library has no global tuning state).
+    x_affine = (scale, shift, relu) with bnstats (AVS_F16X2): x is a RAW activation whose BatchNorm (fp32 [groups, cin],
+    the output's groups) + ReLU the nine-tap kernel applies as it stages x (avs_conv2d_nhwc_bnstats_xin) - the same
+    results as bn_apply on x first; returns None (launching nothing) for the shapes that form does not take."""
     formats = 0
     if isinstance(x, P8):   # AVS_F16P8 input: the 1x1 convolution + statistics form only (the library checks the shape)
         if bnstats is None:
@@ -391,6 +394,28 @@ def conv2d_raw(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x, x_i
     rows = n * ho * wo
     groups = (rows + rpg - 1) // rpg
     need = lib().avs_conv2d_bnstats_workspace_bytes(ctypes.byref(d), int(rpg))
+    if x_affine is not None:
+        if need == _abi.E_UNSUPPORTED:
+            return None
+        xsc, xsf, xrelu = x_affine
+        _dev(xsc, xsf)
+        if xsc.dtype != torch.float32 or xsf.dtype != torch.float32 or not (xsc.is_contiguous() and xsf.is_contiguous()):
+            raise ValueError("x_affine scale / shift must be contiguous fp32 [groups, cin]")
+        if need < 0:
+            check(int(need), "avs_conv2d_bnstats_workspace_bytes")
+        ws = _stats_workspace(x.device, need)
+        scale = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
+        shift = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
+        st = []
+        _timed("conv", dtype, flops, lambda: st.append(
+            lib().avs_conv2d_nhwc_bnstats_xin(ctypes.byref(d), _p(x, x_off), _p(wt), _p(y, y_off), int(rpg), _p(gamma),
+                                              _p(beta), float(eps), _p(scale), _p(shift), _p(ws), ws.numel(), _p(xsc),
+                                              _p(xsf), int(bool(xrelu)), _stream())),
+               cbytes, form=f"convolution + statistics {kh}x{kw}, input affine")
+        if st[0] == _abi.E_UNSUPPORTED:
+            return None
+        check(st[0], "avs_conv2d_nhwc_bnstats_xin")
+        return scale, shift
     if need == _abi.E_UNSUPPORTED:
         if formats:
             check(int(need), "avs_conv2d_bnstats_workspace_bytes")   # no other form reads an AVS_F16P8 input

@@ -172,6 +172,18 @@ int64_t avs_conv2d_bnstats_workspace_bytes(const avs_conv_desc* desc, int64_t ro
 int avs_conv2d_nhwc_bnstats(const avs_conv_desc* desc, const void* d_x, const void* d_w, void* d_y,
                             int64_t rows_per_group, const float* d_gamma, const float* d_beta, float eps,
                             float* d_scale, float* d_shift, void* d_ws, int64_t ws_bytes, avs_stream_t stream);
+/* The same with the input given RAW: x is the raw output of the convolution before, whose BatchNorm (+ ReLU) the kernel
+ * applies as it stages its operand, x'[m,c] = act(x[m,c] * d_in_scale[g,c] + d_in_shift[g,c]), g = m / rows_per_group
+ * (the same groups as the output's), act = ReLU when in_relu, the multiply and the add rounded separately as in
+ * avs_bn_apply; the zero padding is that of x'.  Outputs, scale and shift are bit-identical to avs_bn_apply (in place)
+ * followed by avs_conv2d_nhwc_bnstats, without the apply pass over x.  d_in_scale / d_in_shift: fp32 [groups, cin],
+ * 16-byte aligned.  AVS_F16X2 3x3 / stride 1 / pad 1 convolutions on a dense input at most 63 pixels wide that take the
+ * 256-row tiles (the nine-tap form) only: every other shape returns AVS_E_UNSUPPORTED before launching anything.
+ * The workspace is avs_conv2d_bnstats_workspace_bytes'.                                                          */
+int avs_conv2d_nhwc_bnstats_xin(const avs_conv_desc* desc, const void* d_x, const void* d_w, void* d_y,
+                                int64_t rows_per_group, const float* d_gamma, const float* d_beta, float eps,
+                                float* d_scale, float* d_shift, void* d_ws, int64_t ws_bytes, const float* d_in_scale,
+                                const float* d_in_shift, int in_relu, avs_stream_t stream);
 
 /* Convolution + the WHOLE batch-statistics BatchNorm (+ residual, + ReLU) in one launch, bf16, for equal-sized
  * groups that fit a 256-row output tile whole:
