@@ -17,6 +17,8 @@ this module supplies
 
 The containers deliberately have no torch forward: the product path is HIP only.
 """
+from typing import NamedTuple
+
 import torch
 import torch.nn as nn
 
@@ -106,19 +108,48 @@ class _W:
         return (self.kstep, 1) if self.kstep is not None else (self.rows, 0)
 
 
+class Step(NamedTuple):
+    """One step of the trunk (ResNet50Runner.plan), in launch order.
+    name   torchvision's key of the convolution ("conv1", "layer1.0.conv2", "layer1.0.downsample"); layer 1's shared Gram
+           step is "layer1.0.conv1+downsample"
+    form   how it runs (the class docstring)
+    inp    "finished", or "raw": the input is the previous step's raw output, whose BatchNorm (+ ReLU) this step applies
+           (gram / gram_pair: in its staging; stats: in the nine-tap kernel's staging where the library takes it, else by an
+           apply pass over the input first; split: an apply pass first)
+    out    "finished"; "deferred": the raw output + its affine, applied by the consumer; "p8": stored as AVS_F16P8
+    res    conv3's residual: "none", "identity", "downsample" (finished) or "deferred" (raw, its BatchNorm applied in this
+           step's residual add)
+    block  bottleneck index (-1: the stem)
+    geom   (convolution geometry, input strides, weight row stride) as the avs_conv2d_nhwc* descriptor takes them
+    cluster  the clustered form: tiles per group"""
+    name: str
+    form: str
+    inp: str = "finished"
+    out: str = "finished"
+    res: str = "none"
+    block: int = -1
+    geom: tuple = None
+    cluster: int = 1
+
+
 class ResNet50Runner:
     """Runs the container's parameters on uint8 frames [N,224,224,3] -> fp32 [N,2048].
 
-    Batch-statistics BatchNorm (the reference's mode) has three forms here, chosen per layer; every one
-    of them is deterministic (no float atomics: two runs give bit-identical features):
-      local   bf16, equal-sized groups of <= 256 rows (14x14 / 7x7 maps): convolution + whole BatchNorm (+ residual
-              + ReLU) in ONE launch, statistics inside a tile (avs_conv2d_nhwc_bnlocal) - nothing raw in HBM;
-      gram    bf16 expanding 1x1 layers with 64 / 128 input channels (conv3 / downsample of layers 1-2): statistics
-              from the input's Gram matrix (avs_bn_gram_affine_bf16), then ONE streaming pass with the affine in the
-              epilogue (avs_conv1x1_affine_bf16);
-      twopass other bf16 1x1 layers: one workgroup walks a group twice (avs_conv1x1_bn_bf16);
-      split   convolution (+ per-tile partial statistics in its epilogue for bf16, folded in tile order) or
-              avs_bn_batch_stats -> avs_bn_apply (fp32 parity mode, ragged groups, shapes the other forms decline)."""
+    Batch-statistics BatchNorm (the reference's mode, SURVEY Q2) takes one of these forms per convolution, chosen by plan();
+    every one of them is deterministic (no float atomics: two runs give bit-identical features):
+      local      bf16 / f16x2, equal-sized groups of <= 256 rows (14x14 / 7x7 maps): convolution + whole BatchNorm
+                 (+ residual + ReLU) in ONE launch, statistics inside a tile (avs_conv2d_nhwc_bnlocal) - nothing raw in HBM;
+      cluster    f16x2: the same with a group spread over several tiles that exchange their statistics
+                 (avs_conv2d_nhwc_bncluster);
+      gram       bf16 / f16x2 expanding 1x1 layers with 64 / 128 input channels (conv3 / downsample of layers 1-2):
+                 statistics from the input's Gram matrix, then ONE streaming pass with the affine in the epilogue;
+      gram_pair  layer 1's first conv1 and downsample read the same input: one Gram matrix, one streaming pass each;
+      stats      convolution + per-tile partial statistics in its epilogue, folded in tile order, then an apply pass
+                 (bf16, fp32-split, f16x2: equal groups of >= 64 rows);
+      split      convolution, avs_bn_batch_stats, avs_bn_apply (fp32 parity mode, ragged groups, shapes the others decline);
+      folded     bn_mode="folded": running statistics folded into an apply pass after the convolution.
+    The stem is the fused bf16 (stem_bf16) or f16x2 (stem_f16x2) kernel, or the frames' normalisation + "conv1" in one of
+    the forms above, followed by the max pooling."""
 
     def __init__(self, trunk, dtype=torch.float32, bn_mode="batch", f32_split=False):
         """f32_split (fp32 only): True = activations and weights stay fp32 in HBM, the convolutions' products run on the
@@ -133,32 +164,39 @@ class ResNet50Runner:
         self.f32_split = bool(f32_split) and not self.h2 and dtype == torch.float32
         self.code = ops.dtype_code(dtype, "f16x2" if self.h2 else self.f32_split)   # the contraction entry points
         self.ecode = self.code if self.h2 else ops.dtype_code(dtype)                 # storage format (elementwise kernels)
-        self.fuse_conv_bn = True
-        self.fuse_min_rows, self.fuse_ratio_num, self.fuse_ratio_den = 128, 2, 1
-        self.twopass_max_cin = 128   # wider inputs (256 -> 1024 at 4-frame groups): the second matrix pass costs more than
-                                     # the split form's extra traffic (measured: 4.5 vs 3.4 ms per 8192 frames)
+        self.fuse_conv_bn = True     # bf16: the Gram form for the 1x1 layers of at least fuse_min_rows rows per group whose
+        self.fuse_min_rows, self.fuse_ratio_num, self.fuse_ratio_den = 128, 2, 1   # cout / cin >= num / den (f16x2: >= 2)
         self.bn_local = True         # the one-launch tile-local form where the library takes the shape
-        self.gram_stats = True       # conv3 / downsample of layers 1-2: Gram-matrix statistics + one streaming pass
         self.bn_cluster = True       # AVS_F16X2: groups of several 14x14 maps in ONE launch (tiles exchange their statistics)
         self.fused_stem = True       # uint8 frames -> conv1 -> pooled raw map + partial sums in one kernel
-        self.stem_raw = True         # bn1 + ReLU ride in the staging of layer 1's first conv1 / downsample (both take the
+        self.stem_raw = True         # bf16: bn1 + ReLU ride in the staging of layer 1's first conv1 / downsample (both take the
                                      # one-pass form on ONE Gram matrix of the stem output): no finishing pass
-        self.defer_bn_apply = True   # bn2 + ReLU applied inside conv3's two-pass kernel (avs_conv1x1_bn_in_bf16)
+        self.defer_bn_apply = True   # bn2 + ReLU applied inside conv3's Gram / one-pass kernels
         self.defer_res_apply = True  # the downsample's BatchNorm applied inside conv3's residual add (layer 2's first block)
         self.fold_input_bn = True    # AVS_F16X2: conv1 of the stride-1 bottlenecks stays RAW and its bn1 + ReLU ride in the
                                      # staging of conv2's nine-tap kernel (avs_conv2d_nhwc_bnstats_xin): no apply pass over it
-        self.gram_finish_min_k = 128  # >= this many input channels: the Gram kernel stores the finished input in place, so
-                                      # the convolution pass (N / 128 column slabs) does not transform it per slab
-        self.affine_variant = 0      # tile override of the one-pass 1x1 form (study: _abi.TILE_128 / TILE_256)
-        self.stats_1x1_variant = 0   # tile override of the 1x1 convolution + statistics form (study: _abi.TILE_128 / TILE_256)
+        self.gram_finish_min_k = 128  # bf16, >= this many input channels: the Gram kernel stores the finished input in place,
+                                      # so the convolution pass (N / 128 column slabs) does not transform it per slab
         self.p8_blocks = (0, 1, 3, 4, 5) if self.h2 else ()   # AVS_F16X2: the outputs of these bottlenecks (the inner
                                      # blocks of layers 1-2, whose consumers are the next block's conv1 and residual add - both
                                      # HBM-bound) are stored as AVS_F16P8: fp16 hi + 8-bit remainder, 3 instead of 4 bytes
         self._key = None
         self._w = None
-        self._plans = {}     # (n, group frames) -> per layer: does it take the tile-local form
+        self._plans = {}     # plan key (shapes + switches) -> steps
 
     block_hook = None   # study hook: callable(block index, block output) -> block output
+
+    def _blocks(self):
+        """(torchvision name, Bottleneck) in forward order."""
+        for li in range(4):
+            for b, blk in enumerate(self.trunk[4 + li]):
+                yield f"layer{li + 1}.{b}", blk
+
+    def _pair_ok(self):
+        """Layer 1's first conv1 and downsample read the same input: can ONE Gram matrix give both BatchNorms' statistics?"""
+        b0 = self.trunk[4][0]
+        d = b0.downsample
+        return d is not None and b0.conv1.weight[0].numel() == d[0].weight[0].numel() and b0.bn1.eps == d[1].eps
 
     # weights in kernel layout, rebuilt when the parameters change / move
     def _prepare(self):
@@ -168,39 +206,29 @@ class ResNet50Runner:
         t, dt = self.trunk, self.dtype
         pack = ops.f16x2_pack if self.h2 else (lambda r: r)   # AVS_F16X2: every weight row as fp16 hi | lo runs, once
 
-        def mkw(rows):
-            return _W(pack(rows))
-
-        w = {"stem": mkw(_stem_weight(t[0].weight, 8, dt)), "blocks": []}
-        if self.h2 and tuple(t[0].weight.shape) == (64, 3, 7, 7):
-            # the fused AVS_F16X2 stem: the input normalisation folded into the weights (the constant term in channel 3)
-            w["stem_h2"] = ops.stem_h2_operands(t[0].weight, 1.0, RESNET_MEAN, RESNET_STD)
-
         def bn(m):
             return (m.weight.detach().float().contiguous(), m.bias.detach().float().contiguous(), float(m.eps),
                     m.running_mean.detach().float(), m.running_var.detach().float())
 
-        w["bn1"] = bn(t[1])
-        for li in range(4, 8):
-            for blk in t[li]:
-                d = {"c1": mkw(_ohwi(blk.conv1.weight, dt)), "b1": bn(blk.bn1), "c2": mkw(_ohwi(blk.conv2.weight, dt)),
-                     "b2": bn(blk.bn2), "c3": mkw(_ohwi(blk.conv3.weight, dt)), "b3": bn(blk.bn3),
-                     "stride": blk.stride, "planes": blk.conv1.out_channels}
-                if blk.downsample is not None:
-                    d["cd"] = mkw(_ohwi(blk.downsample[0].weight, dt))
-                    d["bd"] = bn(blk.downsample[1])
-                w["blocks"].append(d)
-        # layer 1's first block: conv1 (64 -> 64) and the downsample (64 -> 256) read the same input, so ONE Gram matrix
-        # gives the batch statistics of both: their weights / BatchNorm parameters stacked for avs_bn_gram_affine_bf16
-        b0 = w["blocks"][0]
-        if "cd" in b0 and b0["c1"].rows.shape[1] == b0["cd"].rows.shape[1] and b0["b1"][2] == b0["bd"][2]:
-            w["cat0"] = (torch.cat([b0["c1"].rows, b0["cd"].rows]).contiguous(),
-                         torch.cat([b0["b1"][0], b0["bd"][0]]).contiguous(),
-                         torch.cat([b0["b1"][1], b0["bd"][1]]).contiguous(), b0["b1"][2], b0["c1"].rows.shape[0])
+        w = {"conv1": (_W(pack(_stem_weight(t[0].weight, 8, dt))), bn(t[1]))}
+        if self.h2 and tuple(t[0].weight.shape) == (64, 3, 7, 7):
+            # the fused AVS_F16X2 stem: the input normalisation folded into the weights (the constant term in channel 3)
+            w["stem_h2"] = ops.stem_h2_operands(t[0].weight, 1.0, RESNET_MEAN, RESNET_STD)
+        for name, blk in self._blocks():
+            convs = [("conv1", blk.conv1, blk.bn1), ("conv2", blk.conv2, blk.bn2), ("conv3", blk.conv3, blk.bn3)]
+            if blk.downsample is not None:
+                convs.append(("downsample", *blk.downsample))
+            for key_, conv, norm in convs:
+                w[f"{name}.{key_}"] = (_W(pack(_ohwi(conv.weight, dt))), bn(norm))
+        if self._pair_ok():
+            # the Gram step's operands: conv1's and the downsample's weights / BatchNorm parameters stacked
+            (c1, b1), (cd, bd) = w["layer1.0.conv1"], w["layer1.0.downsample"]
+            w["layer1.0.conv1+downsample"] = (torch.cat([c1.rows, cd.rows]).contiguous(), torch.cat([b1[0], bd[0]]).contiguous(),
+                                              torch.cat([b1[1], bd[1]]).contiguous(), b1[2], c1.rows.shape[0])
         self._w, self._key = w, key
         return w
 
-    # ---- convolution geometry (shared by the workspace plan and the forward pass) ----
+    # ---- convolution geometry ----
     @staticmethod
     def _stem_geom(n):
         # [N,230,232,4] pre-padded image; conv1 7x7/2 reads 8-pixel (32-element) runs: kh = 7 rows x 32 elements
@@ -211,199 +239,139 @@ class ResNet50Runner:
         ho = (h + 2 * p - k) // s + 1
         return (n, h, h, cin, k, k, s, s, p, p, ho, ho, cout), (h * h * cin, h * cin, cin), k * k * cin
 
-    def _layer_geoms(self, n):
-        """Every convolution of the trunk in forward order: (geometry, x strides, weight row stride)."""
-        yield self._stem_geom(n)
-        h, cin = 56, 64
-        for li, (planes, blocks, stride) in enumerate(((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))):
-            for b in range(blocks):
-                s = stride if b == 0 else 1
-                hout = h // s
-                yield self._nhwc_geom(n, h, cin, 1, 1, 0, planes)
-                yield self._nhwc_geom(n, h, planes, 3, s, 1, planes)
-                if b == 0:
-                    yield self._nhwc_geom(n, h, cin, 1, s, 0, planes * 4)
-                yield self._nhwc_geom(n, hout, planes, 1, 1, 0, planes * 4)
-                h, cin = hout, planes * 4
+    # ---- the plan ----
+    def _gram_ok(self, cin, cout, kh, sh, gmax):
+        """The Gram form: expanding 1x1 / stride-1 layers with 64 / 128 input channels and groups of >= fuse_min_rows
+        rows (measured on MI355X: it wins over the split form where the layer is write-heavy and a group several row
+        tiles long)."""
+        if not (kh == 1 and sh == 1 and gmax >= self.fuse_min_rows and ops.gram_supported(cin, cout)):
+            return False
+        if self.h2:
+            return cout >= 2 * cin
+        return (self.dtype == torch.bfloat16 and self.fuse_conv_bn
+                and cout * self.fuse_ratio_den >= cin * self.fuse_ratio_num)
 
-    def _local_plan(self, n, gsz):
-        """Per layer (forward order): does the one-launch tile-local form take it for n frames in groups of gsz."""
-        key = (n, gsz, self.bn_cluster)
-        plan = self._plans.get(key)
-        if plan is None:
-            dcode = self.code   # (the tile-local form exists for bf16 and f16x2)
-            plan = []
-            for geom, xs, wrs in self._layer_geoms(n):
-                ho, wo, cout = geom[10], geom[11], geom[12]
-                rows = gsz * ho * wo
-                if rows <= 256:
-                    plan.append(ops.conv_bnlocal_tile_rows(dcode, *geom, *xs, wrs, cout, rows) is not None)
-                else:
-                    # a group larger than a tile: the clustered tile-local form where the map splits into k tiles of 193..224
-                    # rows (14 x 14: k = 1, layer 3 with the reference's 4-frame micro-batches; 28 x 28: k = 4) and the group
-                    # into gsz * k <= 16 of them - the tiles of a group exchange their statistics
-                    cl = False
-                    if self.h2 and self.bn_cluster:
-                        cin_l, kh_l = geom[3], geom[4]
-                        for k in (1, 2, 4, 8, 16):
-                            # (maps of several tiles: only the wide 1x1 layer that would otherwise take convolution +
-                            #  statistics + an apply pass - layer 3's first conv1, 512 -> 256 at 28 x 28; measured: layer 2's
-                            #  narrow layers are no faster clustered than on their Gram / nine-tap / 3-byte forms)
-                            if k > 1 and not (kh_l == 1 and cin_l >= 512 and cout >= 256):
-                                continue
-                            if (ho * wo) % k == 0 and 192 < (ho * wo) // k <= 224 and 2 <= gsz * k <= 16:
-                                if ops.conv_bncluster_ok(dcode, *geom, *xs, wrs, cout, rows, gsz * k):
-                                    cl = gsz * k
-                                break
-                    plan.append(cl)
-            if len(self._plans) > 64:
-                self._plans.clear()
-            self._plans[key] = plan
-        return plan
+    def _tile_local(self, geom, gsz, cluster):
+        """1 = the tile-local form takes the layer, k > 1 = the clustered form with groups of k tiles, 0 = neither."""
+        g, xs, wrs = geom
+        cin, kh, ho, wo, cout = g[3], g[4], g[10], g[11], g[12]
+        rows = gsz * ho * wo
+        if rows <= 256:
+            return int(ops.conv_bnlocal_tile_rows(self.code, *g, *xs, wrs, cout, rows) is not None)
+        if not (self.h2 and cluster):
+            return 0
+        # a group larger than a tile: the map splits into k tiles of 193..224 rows (14 x 14: k = 1, layer 3 with the
+        # reference's 4-frame micro-batches; 28 x 28: k = 4) and the group into gsz * k <= 16 of them
+        for k in (1, 2, 4, 8, 16):
+            # (maps of several tiles: only the wide 1x1 layer that would otherwise take convolution + statistics + an
+            #  apply pass - layer 3's first conv1, 512 -> 256 at 28 x 28; measured: layer 2's narrow layers are no faster
+            #  clustered than on their Gram / nine-tap / 3-byte forms)
+            if k > 1 and not (kh == 1 and cin >= 512 and cout >= 256):
+                continue
+            if (ho * wo) % k == 0 and 192 < (ho * wo) // k <= 224 and 2 <= gsz * k <= 16:
+                return gsz * k if ops.conv_bncluster_ok(self.code, *g, *xs, wrs, cout, rows, gsz * k) else 0
+        return 0
 
-    def _twopass_ok(self, cin, cout, kh, sh, gmax):
-        # measured on MI355X: the two-pass kernel wins over the split form where the layer is write-heavy
-        # (cout >= 2*cin: the conv3 / downsample layers) and a group is several row tiles long
-        return (kh == 1 and sh == 1 and self.fuse_conv_bn and gmax >= self.fuse_min_rows
-                and cout * self.fuse_ratio_den >= cin * self.fuse_ratio_num and cin <= self.twopass_max_cin)
+    def plan(self, n, group_frames=None, bn_cluster=None):
+        """The trunk's steps (Step) in launch order for n frames in BatchNorm groups `group_frames` (forward's
+        argument).  bn_cluster: a per-call override of the switch.  From shapes, the trunk's structure, the switches and
+        the library's host-only queries: no weights are touched."""
+        _, gsz, uniform = self._group_sizes(n, group_frames)
+        return self._plan(n, gsz, uniform, self.bn_cluster if bn_cluster is None else bn_cluster)
 
-    def _gram_h2_ok(self, cin, cout, kh, sh, gmax):
-        """AVS_F16X2: the expanding 1x1 layers whose groups are too large for a tile take Gram statistics + one
-        streaming pass (64 / 128 input channels: conv3 of layers 1-2 and layer 1's downsample)."""
-        return (self.h2 and self.gram_stats and kh == 1 and sh == 1 and cin in (64, 128) and cout % 32 == 0
-                and cout >= 2 * cin and gmax >= self.fuse_min_rows)
-
-    def _conv_bn(self, geom, xs, x, wt, bnp, groups, residual=None, relu=True, local=False, algo_k=None, pool=None,
-                 defer=False, in_affine=None, res_affine=None, out_p8=False, x_affine=None):
-        """One convolution + BatchNorm (+ residual, + ReLU) -> NHWC activation; picks the form (class docstring).
-        pool = (k, s, p): a max pooling follows (the stem) - on the split form it is fused with the BatchNorm apply
-        (avs_bn_maxpool_nhwc: the normalised full-resolution map is never written).
-        defer: return (raw convolution, (scale, shift)) WITHOUT applying the BatchNorm - the next layer's two-pass
-        kernel applies it while staging its input (in_affine), so this layer needs no apply pass (bf16, equal groups).
-        res_affine: the residual is a deferred (raw) downsample output; its BatchNorm rides in this layer's residual add
-        (one-pass 1x1 form only).
-        out_p8: the output as an AVS_F16P8 tensor (ops.P8; the one-pass 1x1 form only - the caller has checked that the
-        layer takes it); x / residual may be P8 tensors where the forms that read them take that format.
-        x_affine = (scale, shift): x is the RAW output of the layer before (its `defer` result); its BatchNorm + ReLU are
-        applied inside this layer's nine-tap convolution + statistics kernel where the library takes the shape, else by an
-        apply pass over x in place first (the same values either way)."""
-        n, ho, wo, cout = geom[0], geom[10], geom[11], geom[12]
-        cin, kh, sh = geom[3], geom[4], geom[6]
-        dev, dt = x.device, self.dtype
-        dcode = self.code
-        gamma, beta, eps, rmean, rvar = bnp
-        act = ops.ACT_RELU if relu else ops.ACT_NONE
-        y = torch.empty((n, ho, wo, cout), dtype=dt, device=dev)
-        y2d = y.view(-1, cout)
-
-        def conv(**kw):
-            wsel, layout = wt.conv_operand()
-            if kh == 1 and "bnstats" in kw and self.stats_1x1_variant:
-                kw["variant"] = self.stats_1x1_variant
-            return ops.conv2d_raw(dcode, *geom, x, *xs, wsel, wsel.stride(0), y, cout, algo_k=algo_k,
-                                  algo_in_elems=x.numel() if algo_k is not None else None, w_layout=layout, **kw)
-
-        def pooled(t):
-            k, s, p = pool
-            hp, wp = (ho + 2 * p - k) // s + 1, (wo + 2 * p - k) // s + 1
-            return torch.empty((n, hp, wp, cout), dtype=dt, device=dev), k, s, p
-
-        def finish(scale, shift, grows, gmax):
-            if pool is not None and residual is None:
-                out, k, s, p = pooled(y)
-                return ops.bn_maxpool(y, scale, shift, grows, relu, k, s, p, out, code=self.ecode)
-            ops.bn_apply(y2d, scale, shift, grows, gmax, residual, act, y2d, code=self.ecode)
-            if pool is not None:
-                out, k, s, p = pooled(y)
-                return ops.pool2d(y, "max", k, s, p, out, code=self.ecode)
-            return y
-
-        if self.bn_mode != "batch":
-            conv()
-            scale = (gamma / torch.sqrt(rvar + eps)).contiguous()
-            shift = (beta - rmean * scale).contiguous()
-            return finish(scale.view(1, -1), shift.view(1, -1), None, 0)
-        grows, gmax, uniform = groups[ho * wo]
-        bf16 = dt == torch.bfloat16
-
-        def apply_x():
-            xg = groups[geom[1] * geom[2]]
-            ops.bn_apply(x.view(-1, cin), x_affine[0], x_affine[1], xg[0], xg[1], None, ops.ACT_RELU, x.view(-1, cin),
-                         code=self.ecode)
+    def _plan(self, n, gsz, uniform, cluster):
+        key = (n, gsz, uniform, bool(cluster), self.bn_local, self.fused_stem, self.stem_raw, self.fuse_conv_bn,
+               self.fuse_min_rows, self.fuse_ratio_num, self.fuse_ratio_den, self.defer_bn_apply, self.defer_res_apply,
+               self.fold_input_bn, tuple(self.p8_blocks), self.block_hook is None)
+        steps = self._plans.get(key)
+        if steps is not None:
+            return steps
+        batch, bf16, h2 = self.bn_mode == "batch", self.dtype == torch.bfloat16, self.h2
         # statistics from the convolution's epilogue: the bf16 mode, and the fp32-split mode (whose products already carry
-        # ~2^-15 of error: the E[y^2] - E[y]^2 form on fp32 sums costs nothing next to that); the exact fp32 parity mode
-        # keeps the shifted statistics pass over the stored output
-        fast = uniform and (bf16 or self.f32_split or self.h2)
-        if x_affine is not None and not (fast and self.h2 and not local and in_affine is None and kh == 3):
-            apply_x()   # only the AVS_F16X2 convolution + statistics form takes a raw input
-            x_affine = None
-        if fast and (bf16 or self.h2) and local:
-            cluster = local if (local is not True and int(local) > 1) else 1   # (the plan: True = one group per tile)
-            conv(act=act, bnlocal=(gmax, gamma, beta, eps, residual), cluster=cluster)
-            if pool is not None:
-                out, k, s, p = pooled(y)
-                return ops.pool2d(y, "max", k, s, p, out, code=self.ecode)
-            return y
-        if self.h2 and (in_affine is not None or (fast and not local and self._gram_h2_ok(cin, cout, kh, sh, gmax))):
-            # AVS_F16X2: statistics from the input's second moments (the pass that also applies the BatchNorm + ReLU of
-            # the layer before, in place), then ONE streaming convolution pass with the affine in its epilogue
-            x2d = x.view(-1, cin)
-            sc, sf = ops.bn_gram_affine_h2(x2d, wt.rows, gmax, gamma, beta, eps, in_affine, store_input=in_affine is not None)
-            wsel, layout = wt.conv_operand()
-            if out_p8:
-                y = ops.P8.empty((n, ho, wo, cout), dev)
-            ops.conv2d_affine(dcode, n, geom[1], geom[2], cin, sh, geom[7], ho, wo, cout, x, *xs, wsel, wsel.stride(0), y, cout,
-                              gmax, sc, sf, residual, relu, res_affine, w_layout=layout, variant=self.affine_variant)
-            return y
-        if out_p8 or isinstance(residual, ops.P8):
-            raise RuntimeError("an AVS_F16P8 output / residual belongs to the one-pass 1x1 form")
-        if in_affine is not None or (fast and bf16 and self._twopass_ok(cin, cout, kh, sh, gmax)):
-            # statistics from the input's Gram matrix + ONE streaming pass where the shape allows it (the expanding
-            # 1x1 layers of layers 1-2), else the two-pass kernel
-            if self.gram_stats and ops.gram_supported(cin, cout):
-                ops.conv1x1_gram_bn(x.view(-1, cin), wt.rows, gmax, gamma, beta, eps, y2d, residual, relu, in_affine, res_affine,
-                                    finish_input=cin >= self.gram_finish_min_k)
-            else:
-                assert res_affine is None
-                ops.conv1x1_bn(x.view(-1, cin), wt.rows, gmax, gamma, beta, eps, y2d, residual, relu, in_affine)
-            return y
-        assert res_affine is None
-        affine = None
-        if fast:
-            # statistics from the convolution's epilogue: per-tile partial sums of the fp32 accumulators, folded in
-            # tile order (E[x^2]-E[x]^2: fine for bf16 activations); None = groups too small for that form
-            if x_affine is not None:
-                affine = conv(bnstats=(gmax, gamma, beta, eps), x_affine=(x_affine[0], x_affine[1], True))
-                if affine is None:   # (not the nine-tap form: the apply pass, then the plain one)
-                    apply_x()
-                x_affine = None
-            if affine is None:
-                affine = conv(bnstats=(gmax, gamma, beta, eps))
-        if affine is None and isinstance(x, ops.P8):
-            raise RuntimeError("an AVS_F16P8 input belongs to the convolution + statistics form")
-        if affine is None:
-            # fp32 parity mode / ragged groups / tiny groups (the fused form declined before launching anything):
-            # plain convolution, then the shifted statistics pass over the stored output
-            conv()
-            affine = ops.bn_batch_stats(y2d, grows, gamma, beta, eps, code=self.ecode)
-        if defer:
-            return y, affine
-        return finish(affine[0], affine[1], grows, gmax)
+        # ~2^-15 of error: the E[y^2] - E[y]^2 form on fp32 sums costs nothing next to that), f16x2 (centred sums); the
+        # exact fp32 parity mode keeps the shifted statistics pass over the stored output
+        fast = batch and uniform and (bf16 or self.f32_split or h2)
+        local = self.bn_local and fast and (bf16 or h2)
 
-    def forward(self, frames_u8, group_frames=None, out=None, mid_hook=None):
-        """frames_u8: device uint8 [N,224,224,3] (already 224x224, extractors.py:132).
-        group_frames: int64 CPU tensor / list [G+1] of frame offsets of the BatchNorm micro-batch groups
-        (extractors.py:48-56); default = one group per frame.
-        mid_hook: called (no arguments) once layers 1-2 - the HBM-bound half of the trunk - have been launched and
-        before layers 3-4 - the matrix-core-bound half: the pipeline records a stream event there, so that the next
-        pass (on another stream) runs its memory-bound half under this pass's compute-bound half."""
-        n, h, w_, _ = frames_u8.shape
-        if (h, w_) != (224, 224):
-            raise ValueError("ResNet50Runner expects 224x224 frames (resize first)")
-        if n == 0:
-            return torch.zeros((0, 2048), dtype=torch.float32, device=frames_u8.device)
-        w = self._prepare()
-        dev, dt = frames_u8.device, self.dtype
+        def form(geom, x_p8=False):
+            """(form, cluster) of one convolution + BatchNorm on its own."""
+            g, xs, wrs = geom
+            cin, kh, sh, ho, wo, cout = g[3], g[4], g[6], g[10], g[11], g[12]
+            if not batch:
+                return "folded", 1
+            k = self._tile_local(geom, gsz, cluster) if local else 0
+            if k:
+                return ("local", 1) if k == 1 else ("cluster", k)
+            if fast and self._gram_ok(cin, cout, kh, sh, gsz * ho * wo):
+                return "gram", 1
+            if fast and ops.conv_bnstats_ok(self.code, *g, *xs, wrs, cout, gsz * ho * wo, x_p8=x_p8):
+                return "stats", 1
+            return "split", 1
+
+        split_forms, tiled = ("stats", "split"), ("local", "cluster")
+        pair = self._pair_ok()
+        cpair = self.trunk[4][0].conv1.out_channels + self.trunk[4][0].downsample[0].out_channels if pair else 0
+        x_raw = False    # the block input is the fused stem's RAW pooled map (bn1 + ReLU applied by the Gram step)
+        if self.fused_stem and batch and uniform and bf16:
+            x_raw = (self.stem_raw and self.fuse_conv_bn and pair and ops.gram_supported(64, cpair)
+                     and gsz * 56 * 56 >= self.fuse_min_rows)
+            steps = [Step("conv1", "stem_bf16", out="deferred" if x_raw else "finished")]
+        elif (self.fused_stem and h2 and batch and uniform and tuple(self.trunk[0].weight.shape) == (64, 3, 7, 7) and pair
+              and self._gram_ok(64, cpair, 1, 1, gsz * 56 * 56)):
+            x_raw = True
+            steps = [Step("conv1", "stem_f16x2", out="deferred")]
+        else:
+            geom = self._stem_geom(n)
+            f, k = form(geom)
+            steps = [Step("conv1", f, geom=geom, cluster=k)]
+        blocks = list(self._blocks())
+        h, cin, x_out = 56, 64, "finished"
+        for bi, (name, blk) in enumerate(blocks):
+            s, planes = blk.stride, blk.conv1.out_channels
+            hout = h // s
+            g1 = self._nhwc_geom(n, h, cin, 1, 1, 0, planes)
+            g2 = self._nhwc_geom(n, h, planes, 3, s, 1, planes)
+            gd = self._nhwc_geom(n, h, cin, 1, s, 0, planes * 4) if blk.downsample is not None else None
+            g3 = self._nhwc_geom(n, hout, planes, 1, 1, 0, planes * 4)
+            f1, f2, f3 = form(g1, x_out == "p8"), form(g2), form(g3)
+            fd = form(gd) if gd is not None else None
+            use_pair = bi == 0 and pair and (x_raw or (h2 and fast and f1[0] not in tiled and fd[0] not in tiled
+                                                         and self._gram_ok(cin, planes * 4, 1, 1, gsz * h * h)))
+            # conv1's output stays raw, its bn1 + ReLU applied by conv2 (the nine-tap kernel's staging, else an apply pass)
+            fold1 = (self.fold_input_bn and h2 and uniform and s == 1 and not use_pair and f1[0] in split_forms
+                     and f2[0] in split_forms)
+            # bn2 + ReLU ride in conv3's Gram / one-pass kernels: conv2 only writes its raw output and statistics
+            defer2 = self.defer_bn_apply and f3[0] == "gram" and f2[0] in split_forms
+            # a downsample that would take convolution + statistics + apply keeps its output RAW: its BatchNorm is folded
+            # into conv3's residual add
+            deferd = gd is not None and not use_pair and defer2 and self.defer_res_apply and fd[0] in split_forms
+            # 3-byte storage of this block's output: conv3 is the one-pass form here and the next block's conv1 (dense 1x1
+            # on this output, convolution + statistics) reads that format
+            nxt = blocks[bi + 1][1] if bi + 1 < len(blocks) else None
+            p8 = (bi in self.p8_blocks and h2 and f3[0] == "gram" and self.block_hook is None and nxt is not None
+                  and nxt.stride == 1 and nxt.downsample is None
+                  and form(self._nhwc_geom(n, hout, planes * 4, 1, 1, 0, nxt.conv1.out_channels), True)[0] == "stats")
+            if use_pair:
+                steps.append(Step(name + ".conv1+downsample", "gram_pair", "raw" if x_raw else "finished", block=bi, geom=g1))
+            else:
+                steps.append(Step(name + ".conv1", f1[0], out="deferred" if fold1 else "finished", block=bi, geom=g1,
+                                  cluster=f1[1]))
+            steps.append(Step(name + ".conv2", f2[0], "raw" if fold1 else "finished", "deferred" if defer2 else "finished",
+                              block=bi, geom=g2, cluster=f2[1]))
+            if gd is not None and not use_pair:
+                steps.append(Step(name + ".downsample", fd[0], out="deferred" if deferd else "finished", block=bi, geom=gd,
+                                  cluster=fd[1]))
+            steps.append(Step(name + ".conv3", f3[0], "raw" if defer2 else "finished", "p8" if p8 else "finished",
+                              "deferred" if deferd else "downsample" if gd is not None else "identity", bi, g3, f3[1]))
+            h, cin, x_out, x_raw = hout, planes * 4, steps[-1].out, False
+        if len(self._plans) > 64:
+            self._plans.clear()
+        self._plans[key] = steps = tuple(steps)
+        return steps
+
+    # ---- the executor ----
+    @staticmethod
+    def _group_sizes(n, group_frames):
         if group_frames is None:
             group_frames = torch.arange(n + 1, dtype=torch.int64)
         group_frames = torch.as_tensor(group_frames, dtype=torch.int64)
@@ -411,155 +379,157 @@ class ResNet50Runner:
             raise ValueError("group_frames must start at 0 and end at N")
         sizes = group_frames[1:] - group_frames[:-1]
         gsz = int(sizes.max())
-        uniform = bool((sizes == gsz).all())
-        groups = {hw: ((group_frames * hw).to(dev), gsz * hw, uniform)
-                  for hw in (112 * 112, 56 * 56, 28 * 28, 14 * 14, 7 * 7)}
-        use_local = self.bn_local and self.bn_mode == "batch" and uniform and (dt == torch.bfloat16 or self.h2)
-        plan = iter(self._local_plan(n, gsz)) if use_local else None
+        return group_frames, gsz, bool((sizes == gsz).all())
 
-        def slot():
-            return next(plan) if plan is not None else False
+    def _conv(self, st, w, x, x_aff, groups, residual=None, res_aff=None):
+        """One convolution + BatchNorm (+ residual, + ReLU) in the step's form -> (output, its (scale, shift) when the
+        step's output is deferred, else None).  The stem's max pooling follows (on the split forms fused with the
+        BatchNorm apply: avs_bn_maxpool_nhwc, the normalised full-resolution map is never written)."""
+        (geom, xs, _), (wt, (gamma, beta, eps, rmean, rvar)) = st.geom, w[st.name]
+        n, cin, kh, ho, wo, cout = geom[0], geom[3], geom[4], geom[10], geom[11], geom[12]
+        dev, dt, stem = x.device, self.dtype, st.block < 0
+        relu = not st.name.endswith("downsample")
+        act = ops.ACT_RELU if relu else ops.ACT_NONE
+        grows, gmax = groups[ho * wo]
+        wsel, layout = wt.conv_operand()
+        y = torch.empty((n, ho, wo, cout), dtype=dt, device=dev)
 
-        # stem: (x - mean)/std without /255 (extractors.py:133-139), conv1 7x7/2 pad 3, bn1, ReLU, maxpool 3x3/2
-        stem_local = slot()
-        x_aff = None     # (scale, shift) of bn1 when x is the stem's RAW pooled map (applied by block 0's kernels)
-        if self.fused_stem and self.bn_mode == "batch" and uniform and dt == torch.bfloat16:
-            # one fused launch: the normalised image and the 112x112x64 map never reach HBM.  bn1 + ReLU: a finishing
-            # pass in place, or (stem_raw) inside the staging of the first block's conv1 / downsample
-            gamma, beta, eps = w["bn1"][:3]
-            raw = (self.stem_raw and self.gram_stats and self.fuse_conv_bn and "cat0" in w
-                   and ops.gram_supported(64, w["cat0"][0].shape[0]) and gsz * 56 * 56 >= self.fuse_min_rows)
-            x, sc0, sh0 = ops.stem_conv_bn_pool(frames_u8, w["stem"].rows, 1.0, RESNET_MEAN, RESNET_STD, gsz, gamma, beta, eps,
-                                                apply=not raw)
-            if raw:
-                x_aff = (sc0, sh0)
-        elif (self.fused_stem and self.h2 and self.bn_mode == "batch" and uniform and "stem_h2" in w and "cat0" in w
-              and self._gram_h2_ok(64, w["cat0"][0].shape[0], 1, 1, gsz * 56 * 56)):
-            # AVS_F16X2: one fused launch (uint8 frames -> conv1 on the fp16 matrix cores, two MFMAs per product -> centred
-            # statistics -> the pooled RAW map); bn1 + ReLU are applied by the first block's Gram pass, which reads the map
-            # anyway and stores the finished activation in place
-            gamma, beta, eps = w["bn1"][:3]
-            x, sc0, sh0 = ops.stem_conv_pool_h2(frames_u8, w["stem_h2"], gsz, gamma, beta, eps)
-            x_aff = (sc0, sh0)
+        def pooled():   # the stem's max pooling 3x3 / 2, pad 1
+            return torch.empty((n, (ho + 2 - 3) // 2 + 1, (wo + 2 - 3) // 2 + 1, cout), dtype=dt, device=dev)
+
+        if st.form == "gram":
+            x2d = x.view(-1, cin)
+            if self.h2:
+                # statistics from the input's second moments (the pass that also applies the BatchNorm + ReLU of the layer
+                # before, storing the finished input in place), then ONE streaming pass with the affine in its epilogue
+                sc, sf = ops.bn_gram_affine_h2(x2d, wt.rows, gmax, gamma, beta, eps, x_aff, store_input=x_aff is not None)
+                if st.out == "p8":
+                    y = ops.P8.empty((n, ho, wo, cout), dev)
+                ops.conv2d_affine(self.code, n, geom[1], geom[2], cin, geom[6], geom[7], ho, wo, cout, x, *xs, wsel,
+                                  wsel.stride(0), y, cout, gmax, sc, sf, residual, relu, res_aff, w_layout=layout)
+            else:
+                ops.conv1x1_gram_bn(x2d, wt.rows, gmax, gamma, beta, eps, y.view(-1, cout), residual, relu, x_aff, res_aff,
+                                    finish_input=cin >= self.gram_finish_min_k)
+            return y, None
+
+        def conv(**kw):
+            return ops.conv2d_raw(self.code, *geom, x, *xs, wsel, wsel.stride(0), y, cout, algo_k=147 if stem else None,
+                                  algo_in_elems=x.numel() if stem else None, w_layout=layout, **kw)
+
+        if st.form in ("local", "cluster"):
+            conv(act=act, bnlocal=(gmax, gamma, beta, eps, residual), cluster=st.cluster)
+            return (ops.pool2d(y, "max", 3, 2, 1, pooled(), code=self.ecode) if stem else y), None
+        affine = None
+        if st.form == "folded":
+            conv()
+            scale = (gamma / torch.sqrt(rvar + eps)).contiguous()
+            affine, grows, gmax = (scale.view(1, -1), (beta - rmean * scale).contiguous().view(1, -1)), None, 0
         else:
-            x0 = ops.frames_normalize(frames_u8, dt, 1.0, RESNET_MEAN, RESNET_STD, 230, 232, 3, 3, code=self.ecode)
-            geom, xs, _ = self._stem_geom(n)
-            x = self._conv_bn(geom, xs, x0, w["stem"], w["bn1"], groups, local=stem_local, algo_k=147, pool=(3, 2, 1))
-            del x0
-        hcur = 56
-        for bi, blk in enumerate(w["blocks"]):
-            if bi == 7 and mid_hook is not None:   # blocks 0-2 = layer 1, 3-6 = layer 2
-                mid_hook()
-            s, planes = blk["stride"], blk["planes"]
-            cin = x.shape[3]
-            hout = hcur // s
-            s1, s2 = slot(), slot()
-            sd = slot() if "cd" in blk else False
-            s3 = slot()
-            idn = None
-            aff1 = None   # (scale, shift) of bn1 when t1 is conv1's RAW output
-            if x_aff is not None and self.h2:
-                # AVS_F16X2, first block on the fused stem's RAW pooled map: the Gram pass applies bn1 + ReLU on the way in,
-                # stores the finished activation in place (the identity input of nothing else: conv1 and the downsample
-                # read it) and gives both BatchNorms' affines; then one streaming pass each
-                wcat, gcat, bcat, eps, c1n = w["cat0"]
-                gmax = gsz * hcur * hcur
-                sc, sf = ops.bn_gram_affine_h2(x.view(-1, cin), wcat, gmax, gcat, bcat, eps, in_affine=x_aff, store_input=True)
-                x_aff = None
-                geom, xs, _ = self._nhwc_geom(n, hcur, cin, 1, 1, 0, planes)
-                t1 = torch.empty((n, hcur, hcur, planes), dtype=dt, device=dev)
-                wsel, layout = blk["c1"].conv_operand()
-                ops.conv2d_affine(self.code, n, hcur, hcur, cin, 1, 1, hcur, hcur, planes, x, *xs, wsel, wsel.stride(0), t1,
-                                  planes, gmax, sc[:, :c1n].contiguous(), sf[:, :c1n].contiguous(), None, True, None,
-                                  w_layout=layout)
-                idn = torch.empty((n * hcur * hcur, planes * 4), dtype=dt, device=dev)
-                wsel, layout = blk["cd"].conv_operand()
-                ops.conv2d_affine(self.code, n, hcur, hcur, cin, 1, 1, hcur, hcur, planes * 4, x, *xs, wsel, wsel.stride(0),
-                                  idn, planes * 4, gmax, sc[:, c1n:].contiguous(), sf[:, c1n:].contiguous(), None, False,
-                                  None, w_layout=layout)
-            elif x_aff is not None:
-                # first block on the stem's raw map: one Gram matrix -> the folded affines of conv1 and the downsample,
-                # then one streaming pass each (bn1 + ReLU of the stem applied on the way in)
-                wcat, gcat, bcat, eps, c1n = w["cat0"]
-                x2d, gmax = x.view(-1, cin), gsz * hcur * hcur
-                sc, sh = ops.bn_gram_affine(x2d, wcat, gmax, gcat, bcat, eps, x_aff)
-                t1 = torch.empty((n, hcur, hcur, planes), dtype=dt, device=dev)
-                ops.conv1x1_affine(x2d, blk["c1"].rows, gmax, sc[:, :c1n].contiguous(), sh[:, :c1n].contiguous(),
-                                   t1.view(-1, planes), None, True, x_aff)
-                idn = torch.empty((x2d.shape[0], planes * 4), dtype=dt, device=dev)
-                ops.conv1x1_affine(x2d, blk["cd"].rows, gmax, sc[:, c1n:].contiguous(), sh[:, c1n:].contiguous(), idn, None,
-                                   False, x_aff)
-                x_aff = None
-            elif (bi == 0 and self.h2 and "cat0" in w and self.bn_mode == "batch" and uniform and not s1 and not sd
-                  and self._gram_h2_ok(cin, planes * 4, 1, 1, gsz * hcur * hcur)):
-                # AVS_F16X2, first block: conv1 (64 -> 64) and the downsample (64 -> 256) read the same finished input, so
-                # ONE Gram matrix gives both BatchNorms' affines and each layer is one streaming pass (conv1 would
-                # otherwise take convolution + statistics + an apply pass over its output)
-                wcat, gcat, bcat, eps, c1n = w["cat0"]
-                gmax = gsz * hcur * hcur
-                sc, sf = ops.bn_gram_affine_h2(x.view(-1, cin), wcat, gmax, gcat, bcat, eps)
-                geom, xs, _ = self._nhwc_geom(n, hcur, cin, 1, 1, 0, planes)
-                t1 = torch.empty((n, hcur, hcur, planes), dtype=dt, device=dev)
-                wsel, layout = blk["c1"].conv_operand()
-                ops.conv2d_affine(self.code, n, hcur, hcur, cin, 1, 1, hcur, hcur, planes, x, *xs, wsel, wsel.stride(0), t1,
-                                  planes, gmax, sc[:, :c1n].contiguous(), sf[:, :c1n].contiguous(), None, True, None,
-                                  w_layout=layout)
-                idn = torch.empty((n * hcur * hcur, planes * 4), dtype=dt, device=dev)
-                wsel, layout = blk["cd"].conv_operand()
-                ops.conv2d_affine(self.code, n, hcur, hcur, cin, 1, 1, hcur, hcur, planes * 4, x, *xs, wsel, wsel.stride(0),
-                                  idn, planes * 4, gmax, sc[:, c1n:].contiguous(), sf[:, c1n:].contiguous(), None, False,
-                                  None, w_layout=layout)
+            if x_aff is not None:
+                if st.form == "stats" and kh == 3:
+                    affine = conv(bnstats=(gmax, gamma, beta, eps), x_affine=(x_aff[0], x_aff[1], True))
+                if affine is None:   # (the library's nine-tap form declined: the apply pass over x in place, then the plain one)
+                    xg = groups[geom[1] * geom[2]]
+                    ops.bn_apply(x.view(-1, cin), x_aff[0], x_aff[1], xg[0], xg[1], None, ops.ACT_RELU, x.view(-1, cin),
+                                 code=self.ecode)
+            if st.form == "stats" and affine is None:
+                affine = conv(bnstats=(gmax, gamma, beta, eps))
+            elif st.form == "split":
+                conv()
+                affine = ops.bn_batch_stats(y.view(-1, cout), grows, gamma, beta, eps, code=self.ecode)
+            if st.out == "deferred":
+                return y, affine
+        if stem:
+            return ops.bn_maxpool(y, affine[0], affine[1], grows, relu, 3, 2, 1, pooled(), code=self.ecode), None
+        ops.bn_apply(y.view(-1, cout), affine[0], affine[1], grows, gmax, residual, act, y.view(-1, cout), code=self.ecode)
+        return y, None
+
+    def _gram_pair(self, st, w, x, x_aff, gmax):
+        """Layer 1's first conv1 and downsample: ONE Gram matrix gives both BatchNorms' affines (applying the stem's
+        bn1 + ReLU on the way in when x is its raw map), then one streaming pass each -> (conv1's output, the downsample's
+        as [rows, cout])."""
+        wcat, gcat, bcat, eps, c1n = w[st.name]
+        block = st.name.split(".conv1+")[0]
+        geom, xs, _ = st.geom
+        n, h, cin = geom[0], geom[1], geom[3]
+        x2d = x.view(-1, cin)
+        if self.h2:   # (the finished input is stored in place: the streaming passes read it as it is)
+            sc, sf = ops.bn_gram_affine_h2(x2d, wcat, gmax, gcat, bcat, eps, x_aff, store_input=x_aff is not None)
+        else:
+            sc, sf = ops.bn_gram_affine(x2d, wcat, gmax, gcat, bcat, eps, x_aff)
+        outs = []
+        for part, cols, relu in (("conv1", slice(0, c1n), True), ("downsample", slice(c1n, None), False)):
+            wt = w[f"{block}.{part}"][0]
+            cout = wt.rows.shape[0]
+            y = torch.empty((n, h, h, cout), dtype=self.dtype, device=x.device)
+            if self.h2:
+                wsel, layout = wt.conv_operand()
+                ops.conv2d_affine(self.code, n, h, h, cin, 1, 1, h, h, cout, x, *xs, wsel, wsel.stride(0), y, cout, gmax,
+                                  sc[:, cols].contiguous(), sf[:, cols].contiguous(), None, relu, None, w_layout=layout)
             else:
-                # fold_input_bn: conv1's output stays raw, its bn1 + ReLU applied by conv2 (which falls back to the apply
-                # pass where its shape does not take the nine-tap form)
-                fold1 = (self.fold_input_bn and self.h2 and self.bn_mode == "batch" and uniform and s == 1
-                         and not s1 and not s2)
-                geom, xs, _ = self._nhwc_geom(n, hcur, cin, 1, 1, 0, planes)
-                t1 = self._conv_bn(geom, xs, x, blk["c1"], blk["b1"], groups, local=s1, defer=fold1)
-                if isinstance(t1, tuple):
-                    t1, aff1 = t1
-            # bn2 + ReLU ride in conv3's input staging when conv3 takes the two-pass kernel: conv2 then only
-            # writes its raw output and statistics (no apply pass over it)
-            gmax3 = gsz * hout * hout
-            defer2 = (self.defer_bn_apply and self.bn_mode == "batch" and uniform and not s2 and not s3 and
-                      ((dt == torch.bfloat16 and planes <= 512 and self._twopass_ok(planes, planes * 4, 1, 1, gmax3))
-                       or self._gram_h2_ok(planes, planes * 4, 1, 1, gmax3)))
-            geom, xs, _ = self._nhwc_geom(n, hcur, planes, 3, s, 1, planes)
-            t2 = self._conv_bn(geom, xs, t1, blk["c2"], blk["b2"], groups, local=s2, defer=defer2, x_affine=aff1)
-            aff2 = None
-            if defer2:
-                t2, aff2 = t2
-            del t1
-            affd = None
-            if idn is not None:
-                pass
-            elif "cd" in blk:
-                # a downsample branch that would take convolution + statistics + apply keeps its output RAW when conv3
-                # is the one-pass form: its BatchNorm is folded into conv3's residual add
-                deferd = (defer2 and self.defer_res_apply and not sd and self.gram_stats
-                          and ops.gram_supported(planes, planes * 4)
-                          and not self._twopass_ok(cin, planes * 4, 1, s, gsz * hout * hout))
-                geom, xs, _ = self._nhwc_geom(n, hcur, cin, 1, s, 0, planes * 4)
-                idn = self._conv_bn(geom, xs, x, blk["cd"], blk["bd"], groups, relu=False, local=sd, defer=deferd)
-                if deferd:
-                    idn, affd = idn
-                idn = idn.view(-1, planes * 4)
+                ops.conv1x1_affine(x2d, wt.rows, gmax, sc[:, cols].contiguous(), sf[:, cols].contiguous(), y.view(-1, cout),
+                                   None, relu, x_aff)
+            outs.append(y)
+        return outs[0], outs[1].view(-1, outs[1].shape[3])
+
+    def forward(self, frames_u8, group_frames=None, out=None, mid_hook=None, bn_cluster=None):
+        """frames_u8: device uint8 [N,224,224,3] (already 224x224, extractors.py:132).
+        group_frames: int64 CPU tensor / list [G+1] of frame offsets of the BatchNorm micro-batch groups
+        (extractors.py:48-56); default = one group per frame.
+        mid_hook: called (no arguments) once layers 1-2 - the HBM-bound half of the trunk - have been launched and
+        before layers 3-4 - the matrix-core-bound half: the pipeline records a stream event there, so that the next
+        pass (on another stream) runs its memory-bound half under this pass's compute-bound half.
+        bn_cluster: this call's choice of the clustered form (None: the runner's switch)."""
+        n, h, w_, _ = frames_u8.shape
+        if (h, w_) != (224, 224):
+            raise ValueError("ResNet50Runner expects 224x224 frames (resize first)")
+        if n == 0:
+            return torch.zeros((0, 2048), dtype=torch.float32, device=frames_u8.device)
+        group_frames, gsz, uniform = self._group_sizes(n, group_frames)
+        steps = self._plan(n, gsz, uniform, self.bn_cluster if bn_cluster is None else bn_cluster)
+        w = self._prepare()
+        dev = frames_u8.device
+        groups = {hw: ((group_frames * hw).to(dev), gsz * hw) for hw in (112 * 112, 56 * 56, 28 * 28, 14 * 14, 7 * 7)}
+        x = x_aff = t = t_aff = idn = idn_aff = None
+        for st in steps:
+            part = st.name.rsplit(".", 1)[-1]
+            if part in ("conv1", "conv1+downsample") and st.block == 7 and mid_hook is not None:
+                mid_hook()   # (blocks 0-2 = layer 1, 3-6 = layer 2)
+            if st.form == "stem_bf16":
+                # one fused launch: the normalised image and the 112x112x64 map never reach HBM.  bn1 + ReLU: a finishing
+                # pass in place, or inside the staging of the first block's Gram step
+                gamma, beta, eps = w["conv1"][1][:3]
+                x, sc0, sh0 = ops.stem_conv_bn_pool(frames_u8, w["conv1"][0].rows, 1.0, RESNET_MEAN, RESNET_STD, gsz, gamma,
+                                                    beta, eps, apply=st.out == "finished")
+                x_aff = (sc0, sh0) if st.out == "deferred" else None
+            elif st.form == "stem_f16x2":
+                # one fused launch (uint8 frames -> conv1 on the fp16 matrix cores -> centred statistics -> the pooled RAW
+                # map); bn1 + ReLU are applied by the first block's Gram step, which stores the finished map in place
+                gamma, beta, eps = w["conv1"][1][:3]
+                x, sc0, sh0 = ops.stem_conv_pool_h2(frames_u8, w["stem_h2"], gsz, gamma, beta, eps)
+                x_aff = (sc0, sh0)
+            elif st.block < 0:
+                # (x - mean)/std without /255 (extractors.py:133-139), conv1 7x7/2 pad 3, bn1, ReLU, maxpool 3x3/2
+                x0 = ops.frames_normalize(frames_u8, self.dtype, 1.0, RESNET_MEAN, RESNET_STD, 230, 232, 3, 3, code=self.ecode)
+                x = self._conv(st, w, x0, None, groups)[0]
+                del x0
+            elif part == "conv1+downsample":
+                t, idn = self._gram_pair(st, w, x, x_aff, groups[st.geom[0][1] ** 2][1])
+                x_aff = None
+            elif part == "conv1":
+                t, t_aff = self._conv(st, w, x, None, groups)
+            elif part == "conv2":
+                t, t_aff = self._conv(st, w, t, t_aff, groups)
+            elif part == "downsample":
+                idn, idn_aff = self._conv(st, w, x, None, groups)
+                idn = idn.view(-1, idn.shape[3])
             else:
-                idn = x if isinstance(x, ops.P8) else x.view(-1, cin)
-            geom, xs, _ = self._nhwc_geom(n, hout, planes, 1, 1, 0, planes * 4)
-            # 3-byte storage of this block's output: conv3 is the one-pass form here and so is the next block's (same
-            # layer), whose conv1 is the convolution + statistics form on dense rows
-            p8 = (bi in self.p8_blocks and self.bn_mode == "batch" and uniform and not s3 and self.block_hook is None
-                  and (aff2 is not None or self._gram_h2_ok(planes, planes * 4, 1, 1, gmax3)) and (planes * 4) % 32 == 0
-                  # ... and the READER agrees: the next block's conv1 (dense 1x1 on this output, convolution + statistics)
-                  and bi + 1 < len(w["blocks"]) and w["blocks"][bi + 1]["stride"] == 1 and "cd" not in w["blocks"][bi + 1]
-                  and ops.conv_bnstats_p8_input_ok(self.code, n, hout, planes * 4, w["blocks"][bi + 1]["planes"], gmax3))
-            x = self._conv_bn(geom, xs, t2, blk["c3"], blk["b3"], groups, residual=idn, relu=True, local=s3,
-                              in_affine=aff2, res_affine=affd, out_p8=p8)
-            del t2, idn
-            if self.block_hook is not None:   # study tools only (tools/h3_storage_study.py): a block output's storage format
-                x = self.block_hook(bi, x)
-            hcur = hout
+                if st.res == "identity":
+                    idn = x if isinstance(x, ops.P8) else x.view(-1, x.shape[3])
+                x, _ = self._conv(st, w, t, t_aff, groups, idn, idn_aff)
+                t = t_aff = idn = idn_aff = None
+                if self.block_hook is not None:   # study tools only (tools/h3_storage_study.py): a block output's storage format
+                    x = self.block_hook(st.block, x)
         return ops.global_avgpool(x, out, code=self.ecode)
 
 

@@ -12,7 +12,7 @@ from ._abi import (ACT_NONE, ACT_RELU, AVS_BF16, AVS_F16X2, AVS_F32, AVS_F32_SPL
                    lib)
 
 __all__ = [
-    "ACT_NONE", "ACT_RELU", "linear", "gemm_nt_batched", "conv2d", "conv2d_raw", "conv2d_split", "conv_bnlocal_tile_rows", "conv_bncluster_ok", "cluster_exchange_errors", "lstm_split_errors", "conv1x1_bn", "conv1x1_gram_bn", "bn_gram_affine", "gram_supported", "frames_normalize", "pull_copy", "stem_conv_bn_pool", "stem_h2_operands", "stem_conv_pool_h2", "resize_bilinear",
+    "ACT_NONE", "ACT_RELU", "linear", "gemm_nt_batched", "conv2d", "conv2d_raw", "conv2d_split", "conv_bnlocal_tile_rows", "conv_bncluster_ok", "conv_bnstats_ok", "cluster_exchange_errors", "lstm_split_errors", "conv1x1_bn", "conv1x1_gram_bn", "bn_gram_affine", "gram_supported", "frames_normalize", "pull_copy", "stem_conv_bn_pool", "stem_h2_operands", "stem_conv_pool_h2", "resize_bilinear",
     "bn_batch_stats", "bn_apply", "bn_maxpool", "pool2d", "global_avgpool", "segment_mean", "hsv_frame_diff", "reflect_pad", "stft_f64", "stft_mel_fused", "power_mel",
     "clamp_topdb", "stft_mel_max", "stft_mel_segmean", "stft_mel_segmean_batch", "stft_mel_shots", "vggish_examples", "fill", "quantize", "resample", "lstm", "mha_batchaxis", "score_head", "mhsa_flash", "softmax_rows", "cdist", "dtw_path",
     "gather_scale", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
@@ -262,11 +262,13 @@ def conv_bncluster_ok(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout,
     return True
 
 
-def conv_bnstats_p8_input_ok(dtype, n, h, cin, cout, rows_per_group):
-    """Does avs_conv2d_nhwc_bnstats take a dense 1x1 / stride-1 convolution [n,h,h,cin] -> cout with an AVS_F16P8 INPUT?
-    (the planner's question before it stores a block output in that format: the next block's conv1 is the reader)"""
-    d = _abi.ConvDesc(dtype, n, h, h, cin, 1, 1, 1, 1, 0, 0, h, h, cout, h * h * cin, h * cin, cin, cin, cout, ACT_NONE, 1.0,
-                      0, 0, _abi.X_F16P8)
+def conv_bnstats_ok(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x_img_stride, x_row_stride, x_px_stride,
+                    w_row_stride, y_px_stride, rows_per_group, x_p8=False):
+    """Does avs_conv2d_nhwc_bnstats take this convolution (x_p8: with an AVS_F16P8 input) for groups of rows_per_group
+    rows?  A host-only query (the planner's question): the library declines groups of < 64 rows, and an AVS_F16P8 input
+    outside the dense 1x1 / stride-1 shapes."""
+    d = _abi.ConvDesc(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x_img_stride, x_row_stride, x_px_stride,
+                      w_row_stride, y_px_stride, ACT_NONE, 1.0, 0, 0, _abi.X_F16P8 if x_p8 else 0)
     r = lib().avs_conv2d_bnstats_workspace_bytes(ctypes.byref(d), int(rows_per_group))
     if r == _abi.E_UNSUPPORTED:
         return False

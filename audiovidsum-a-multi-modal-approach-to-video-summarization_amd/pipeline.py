@@ -114,12 +114,6 @@ class FrameScoringPipeline:
         # half (layers 3-4) of the other.  Passes are independent (disjoint frames, disjoint rows of the output).
         self.streams = int(streams)
         self._side = None
-        if self.streams == 2:
-            # kernels whose workgroups WAIT for each other (the clustered BatchNorm) rely on one queue's in-order dispatch: a
-            # group's workgroups are dispatched together, complete groups always finish.  Two queues feeding the chip at once can
-            # each hold partial groups that fill the CUs and wait for partners the other queue's partial groups keep out - the
-            # bounded waits would end it and score() would raise.  Two-stream passes therefore keep to the unclustered forms
-            visual_extractor._resnet_runner.bn_cluster = False
 
     def _group_offsets(self, video_offsets):
         """BatchNorm groups never straddle a video: per video, groups of frames_per_group (+ remainder)."""
@@ -265,8 +259,14 @@ class FrameScoringPipeline:
                 if mid_prev is not None:
                     st.wait_event(mid_prev)
                 mid = torch.cuda.Event()
+                # kernels whose workgroups WAIT for each other (the clustered BatchNorm) rely on one queue's in-order
+                # dispatch: a group's workgroups are dispatched together, complete groups always finish.  Two queues feeding
+                # the chip at once can each hold partial groups that fill the CUs and wait for partners the other queue's
+                # partial groups keep out - the bounded waits would end it and score() would raise.  Overlapped passes
+                # therefore keep to the unclustered forms
                 with torch.cuda.stream(st):
-                    self.visual._resnet_runner.forward(chunk, groups, out=out[:, :2048], mid_hook=lambda: mid.record(st))
+                    self.visual._resnet_runner.forward(chunk, groups, out=out[:, :2048], mid_hook=lambda: mid.record(st),
+                                                       bn_cluster=False)
                 chunk.record_stream(st)
                 mid_prev = mid
                 continue

@@ -733,18 +733,30 @@ def test_conv_bnlocal_declines(dev):
 
 
 @pytest.mark.parametrize("gsize", [1, 4])
-def test_resnet50_bf16_local_form_close_to_split_form(dev, gsize):
+def test_resnet50_bf16_planned_local_form_close_to_split_form(dev, gsize, monkeypatch):
     """Whole trunk: one-launch convolution + BatchNorm on the layers that take it against the two-pass / split forms
     (both bf16) and fp32."""
+    from avsum_amd import ops
     from avsum_amd.cnn import ResNet50Runner, resnet50_trunk
     torch.manual_seed(23)
     trunk = resnet50_trunk().to(dev)
     frames = torch.from_numpy(_frames(16, 4)).to(dev)
     groups = list(range(0, 17, gsize))
     local = ResNet50Runner(trunk, torch.bfloat16)
+    launched = []
+    raw = ops.conv2d_raw
+
+    def spy(*a, **k):
+        if k.get("bnlocal") is not None:
+            launched.append(k.get("cluster", 1))
+        return raw(*a, **k)
+
+    monkeypatch.setattr(ops, "conv2d_raw", spy)
     got = local.forward(frames, groups).cpu()
-    plan = local._plans[(16, gsize, local.bn_cluster)]
-    assert sum(plan) == (28 if gsize == 1 else 9)     # the form really ran (14x14 + 7x7 layers / 7x7 layers)
+    monkeypatch.undo()
+    # the form really ran (14x14 + 7x7 layers / 7x7 layers), as the plan says
+    assert len(launched) == (28 if gsize == 1 else 9)
+    assert sum(s.form in ("local", "cluster") for s in local.plan(16, groups)) == len(launched)
     split = ResNet50Runner(trunk, torch.bfloat16)
     split.bn_local = False
     ref_bf = split.forward(frames, groups).cpu()

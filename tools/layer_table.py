@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-layer accounting of the production ResNet-50 forward (bf16, batch-statistics BatchNorm, per-frame groups unless
---gf): every `_conv_bn` call (convolution + BatchNorm + residual + ReLU in whichever form the runner picks) and the
-stem are bracketed with events IN PLACE, so the table is the real pass, not isolated kernels.
+--gf): every step of the runner's plan (convolution + BatchNorm + residual + ReLU in the step's form; the first block's
+shared Gram step as its Gram matrix + one row per convolution) and the stem are bracketed with events IN PLACE, so the table
+is the real pass, not isolated kernels.
 
 Per layer: time per pass, matrix rate (algorithmic FLOP / time), stream rate (bf16 input + output + residual bytes /
 time) and the time an ideal kernel would take: max(FLOP / 1.2 PFLOP/s, bytes / 5.5 TB/s) - 1.2 PF is what the LDS-DMA
@@ -46,7 +47,7 @@ frames = torch.randint(0, 256, (args.n, 224, 224, 3), dtype=torch.uint8, device=
 gf = torch.arange(0, args.n + 1, args.gf, dtype=torch.int64)
 
 records = []
-orig_conv_bn = cnn.ResNet50Runner._conv_bn
+orig_conv = cnn.ResNet50Runner._conv
 orig_stem = ops.stem_conv_bn_pool
 
 
@@ -54,20 +55,19 @@ def ev():
     return torch.cuda.Event(enable_timing=True)
 
 
-def timed_conv_bn(self, geom, xs, x, wt, bnp, groups, residual=None, **kw):
+def timed_conv(self, st, w, x, x_aff, groups, residual=None, res_aff=None):
     e0, e1 = ev(), ev()
     e0.record()
-    out = orig_conv_bn(self, geom, xs, x, wt, bnp, groups, residual=residual, **kw)
+    out = orig_conv(self, st, w, x, x_aff, groups, residual, res_aff)
     e1.record()
+    geom = st.geom[0]
     n, h, cin, kh, sh, ho, cout = geom[0], geom[1], geom[3], geom[4], geom[6], geom[10], geom[12]
-    kk = kw.get("algo_k") or kh * geom[5] * cin
+    kk = (147 if st.block < 0 else kh * geom[5] * cin)
     rows = n * ho * geom[11]
     flops = 2.0 * rows * kk * cout
     in_elems = n * h * h * cin if sh == 1 or kh > 1 else rows * cin
     byts = (in_elems + rows * cout * (2 if residual is not None else 1)) * es
-    loc = kw.get("local")
-    form = ("cluster" if (loc and loc is not True and int(loc) > 1) else "local" if loc else "gram/2pass" if (kw.get("in_affine") is not None or (
-        kh == 1 and cout >= 2 * cin and sh == 1)) else "split+defer" if kw.get("defer") else "split")
+    form = st.form + ("+defer" if st.out == "deferred" else "")
     records.append((f"{h}x{h} {kh}x{kh}/{sh} {cin}->{cout}" + (" +res" if residual is not None else ""), form,
                     flops, byts, e0, e1))
     return out
@@ -85,19 +85,18 @@ def timed_stem(frames_u8, *a, **kw):
 
 
 inside = [0]
-_inner_conv_bn = timed_conv_bn
 
 
-def timed_conv_bn_outer(self, *a, **kw):
+def timed_conv_outer(self, *a, **kw):
     inside[0] += 1
     try:
-        return _inner_conv_bn(self, *a, **kw)
+        return timed_conv(self, *a, **kw)
     finally:
         inside[0] -= 1
 
 
 def timed_op(fn, label):
-    # the first block's kernels on the stem's raw map are called from forward() directly, not through _conv_bn
+    # the first block's shared Gram step (bf16): its Gram matrix and one streaming pass per convolution
     def wrapper(x2d, wt, rpg, *a, **kw):
         if inside[0]:
             return fn(x2d, wt, rpg, *a, **kw)
@@ -117,7 +116,7 @@ def timed_op(fn, label):
 
 
 def timed_h2(fn, label):
-    # AVS_F16X2: the first block's Gram matrix + its two streaming passes are called from forward() directly
+    # AVS_F16X2: the first block's shared Gram step: its Gram matrix and one streaming pass per convolution
     def wrapper(*a, **kw):
         if inside[0]:
             return fn(*a, **kw)
@@ -137,7 +136,7 @@ def timed_h2(fn, label):
     return wrapper
 
 
-cnn.ResNet50Runner._conv_bn = timed_conv_bn_outer
+cnn.ResNet50Runner._conv = timed_conv_outer
 ops.bn_gram_affine_h2 = timed_h2(ops.bn_gram_affine_h2, "gram")
 ops.conv2d_affine = timed_h2(ops.conv2d_affine, "affine")
 ops.stem_conv_bn_pool = timed_stem
