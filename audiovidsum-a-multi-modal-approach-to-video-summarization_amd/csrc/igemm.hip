@@ -1719,354 +1719,347 @@ static bool igemm_taps_ok(const IgemmParams& p) {
          p.cin % 16 == 0 && (long long)(384 + 64) * p.x_px_stride * 4 + (long long)p.cin * 4 < (1ll << 31);
 }
 
-// every dispatcher returns whether a kernel was launched: a (dtype, tile, epilogue) combination that has no instantiation
-// is an error of the launcher's rules, reported as AVS_E_UNSUPPORTED - never a silent AVS_OK with an untouched output
+// FASTK (the scalar tap walk over buffer_load ... lds): cin a whole number of reduction steps of bke elements, at most 32
+// taps, and the buffer window below 2 GiB
+static bool igemm_fastk_ok(const IgemmParams& p, long long lin_stride, int es, int bke, int bn) {
+  return !(p.variant & AVS_STAGING_GENERIC) && igemm_buffer_window_ok(p, lin_stride, es, bn) && p.cin % bke == 0 &&
+         p.K % bke == 0 && p.K / p.cin <= 32 && p.K % p.cin == 0;
+}
+
+// ---- which kernel, and why ----
+// igemm_plan() validates the shape and chooses everything there is to choose, from the dtype, the geometry and the options in
+// p alone - `stats` (a statistics workspace is given) and `in_affine` (an input affine is given) stand for the only operands
+// whose presence matters; no pointer of p is read, so the host queries plan with no operands at all.  Top to bottom: the
+// checks, the tile (few_f32, narrow, wide96, the tall rule, the affine override), the AVS_F16P8 requirements, the grid,
+// the input walk (spatial, lin_stride), the 224-row tile, then igemm_kernel's arguments in the order they depend on each
+// other.  The checks that need the operands themselves are igemm_run's; pl.operand_checks keeps their places among these.
+#define AVS_PLAN_REQUIRE(cond, code, ...) \
+  do {                                    \
+    if (!(cond)) {                        \
+      avs_set_error(__VA_ARGS__);         \
+      return pl.status = (code);          \
+    }                                     \
+  } while (0)
+static int igemm_plan(int dtype, const IgemmParams& p, int batch, bool stats, bool in_affine, const char* who,
+                      IgemmPlan& pl) {
+  pl = IgemmPlan{};
+  pl.dtype = dtype;
+  pl.batch = batch;
+  pl.in_affine = in_affine;
+  const int es = pl.es = dtype == AVS_BF16 ? 2 : 4;
+  pl.split = dtype == AVS_F32_SPLIT ? 1 : (dtype == AVS_F16X2 ? 2 : 0);
+  pl.acc64 = dtype == AVS_F32_ACC64;
+  const int ce = dtype == AVS_F16X2 ? 8 : 16 / es;   // AVS_F16X2: whole hi | lo runs of 8 slots
+  AVS_PLAN_REQUIRE(dtype == AVS_F32 || dtype == AVS_BF16 || dtype == AVS_F32_ACC64 || dtype == AVS_F32_SPLIT ||
+                       dtype == AVS_F16X2, AVS_E_ARG, "%s: bad dtype %d", who, dtype);
+  if (dtype == AVS_F16X2) {
+    const bool fixed = p.alpha == 1.0f &&
+                       ((p.bias_mode == AVS_BIAS_NONE && (p.act == AVS_ACT_NONE || p.tile_rows || p.affine)) ||
+                        (p.bias_mode == AVS_BIAS_COL && p.act == AVS_ACT_RELU && !stats && !p.tile_rows && !p.affine));
+    AVS_PLAN_REQUIRE(fixed, AVS_E_UNSUPPORTED,
+                     "%s: AVS_F16X2 takes alpha = 1 and either no bias / activation (or a BatchNorm form) or bias per column + ReLU", who);
+    AVS_PLAN_REQUIRE(p.N % 8 == 0 && p.ldc % 8 == 0 && (p.sC % 8) == 0, AVS_E_SHAPE,
+                     "%s: AVS_F16X2 needs cout and the output strides in multiples of 8 slots", who);
+  }
+  pl.operand_checks = 1;   // (AVS_F16X2 operands 32-byte aligned)
+  AVS_PLAN_REQUIRE(p.M >= 0 && p.N > 0 && p.K > 0 && batch > 0, AVS_E_SHAPE, "%s: bad sizes M=%d N=%d K=%d batch=%d", who,
+                   p.M, p.N, p.K, batch);
+  if (p.M == 0) return AVS_OK;   // nothing to launch: pl.grid = 0
+  pl.operand_checks = 2;   // (x, w, y given; a bias where the mode names one)
+  AVS_PLAN_REQUIRE(p.cin % ce == 0 && p.K % ce == 0, AVS_E_SHAPE,
+                   "%s: cin=%d / K=%d must be multiples of %d elements (16 bytes)", who, p.cin, p.K, ce);
+  pl.operand_checks = 3;   // (x, w 16-byte aligned)
+  AVS_PLAN_REQUIRE((p.x_img_stride * es) % (ce * es) == 0 && (p.x_row_stride * es) % (ce * es) == 0 &&
+                       (p.x_px_stride * es) % (ce * es) == 0 && (p.ldb * es) % (ce * es) == 0 && (p.sA * es) % (ce * es) == 0 &&
+                       (p.sB * es) % (ce * es) == 0,
+                   AVS_E_ALIGN, "%s: strides must be multiples of %d bytes", who, ce * es);
+  if (p.nsplit > 0) {                                             // two destinations: each row stride covers its own columns
+    AVS_PLAN_REQUIRE(p.ldc >= p.nsplit && p.ldc2 >= p.N - p.nsplit, AVS_E_SHAPE,
+                     "%s: output row strides %lld / %lld < the %d / %d columns of the two destinations", who, p.ldc, p.ldc2,
+                     p.nsplit, p.N - p.nsplit);
+  } else {
+    AVS_PLAN_REQUIRE(p.ldc >= p.N, AVS_E_SHAPE, "%s: output row stride %lld < N=%d", who, p.ldc, p.N);
+  }
+  AVS_PLAN_REQUIRE(batch <= 65535, AVS_E_SHAPE, "%s: batch %d > 65535", who, batch);
+
+  const int tile_mode = p.variant & 3;   // AVS_TILE_AUTO: by rule; AVS_TILE_128: never 256 rows; AVS_TILE_256: wherever they exist
+  const bool brelu = p.alpha == 1.0f && p.bias_mode == AVS_BIAS_COL && p.act == AVS_ACT_RELU && !stats;
+  // exact fp32 with few tiles (the scorer's linear layers and their gradients: 1800 rows x 512 .. 2048 columns = 16 .. 240
+  // tiles of 128 x 128 on 256 CUs x 3 workgroups): 64-wide column tiles double the workgroups; the same sums in the same order
+  const bool few_f32 = dtype == AVS_F32 && batch == 1 && !stats && !p.tile_rows && !p.affine &&
+                       (((long long)p.M + 127) / 128) * ((p.N + 127) / 128) < 256;
+  const bool narrow = p.N <= 64 || dtype == AVS_F32_ACC64 || few_f32;
+  pl.bn = narrow ? 64 : 128;
+  pl.tiles_n = (p.N + pl.bn - 1) / pl.bn;
+  // AVS_F16X2 bias + ReLU (Inception-v3's folded-BatchNorm convolutions): cout = 96, 160, 192, 288 ... leave a 128-wide
+  // column tile 25 - 37 % empty; 96-wide tiles on the 256-row form when they save at least 15 % of the padded width and the
+  // 256-row rule below holds for them (a tuning choice: the outputs do not depend on it; AVS_TILE_128 keeps the 128-row tiles)
+  bool wide96 = false;
+  if (dtype == AVS_F16X2 && !narrow && brelu && !p.tile_rows && !p.affine && batch == 1 && g_pipe3 &&
+      (long long)p.K * 4 >= g_tall_min_k_bytes && (tile_mode == AVS_TILE_AUTO || tile_mode == AVS_TILE_256)) {
+    const int t96 = (p.N + 95) / 96;
+    const long long tall_tiles96 = ((long long)p.M + 255) / 256 * t96;
+    if (t96 * 96 * 100 <= pl.tiles_n * 128 * 85 && (tile_mode == AVS_TILE_256 || tall_tiles96 >= g_tall_min_tiles)) {
+      wide96 = true;
+      pl.bn = 96;
+      pl.tiles_n = t96;
+    }
+  }
+  // 256-row tiles (WR = 4): bf16, the compile-time epilogue forms, a reduction of at least three 64-byte steps (the
+  // variants are built on the 3-buffer pipeline), and enough rows that the grid still fills the chip several times
+  {
+    const bool fixed_epi = (p.alpha == 1.0f && p.bias_mode == AVS_BIAS_NONE && p.act == AVS_ACT_NONE) || brelu;
+    const bool can = (dtype == AVS_BF16 || dtype == AVS_F32_SPLIT || dtype == AVS_F16X2) && fixed_epi && g_pipe3 &&
+                     (long long)p.K * es > 128 && batch == 1;
+    const long long tall_tiles = ((long long)p.M + 255) / 256 * pl.tiles_n;
+    AVS_PLAN_REQUIRE(tile_mode != AVS_TILE_224 || p.tile_rows, AVS_E_UNSUPPORTED,
+                     "%s: AVS_TILE_224 is a tile of the tile-local BatchNorm form (avs_conv2d_nhwc_bnlocal)", who);
+    pl.tall = wide96 || (can && (tile_mode == AVS_TILE_256 || (tile_mode == AVS_TILE_AUTO && tall_tiles >= g_tall_min_tiles &&
+                                                                (narrow || (long long)p.K * es >= g_tall_min_k_bytes))));
+  }
+  // EPI_BNLOCAL (validated by bnlocal_plan): 256-row tiles at a pitch of tile_rows
+  if (p.tile_rows) pl.tall = true;
+  // AVS_F16P8 operands: the input of the 1x1 convolution + statistics form on the 256-row tiles (A fragments in registers),
+  // the output / residual of the given-affine form
+  AVS_PLAN_REQUIRE(!(p.y_p8 || p.res_p8) || (p.affine && p.N % 16 == 0 && p.ldc % 16 == 0 && p.ldr % 16 == 0), AVS_E_UNSUPPORTED,
+                   "%s: an AVS_F16P8 output / residual is taken by avs_conv2d_nhwc_affine (cout and row strides in multiples of 16)", who);
+  if (p.x_p8) {
+    AVS_PLAN_REQUIRE(stats && !p.tile_rows && !p.affine && batch == 1 && g_pipe3 && !(p.variant & AVS_STAGING_GENERIC) &&
+                         (pl.tall || (long long)p.K * 4 <= g_rowb_threshold_bytes) &&   // (64-byte reduction steps)
+                         p.KW == 1 && p.K == p.cin && p.K % 32 == 0 && p.K >= 64 &&
+                         p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 && p.x_row_stride == (long long)p.Wo * p.x_px_stride &&
+                         p.x_img_stride == (long long)p.HoWo * p.x_px_stride && p.x_px_stride % 16 == 0 &&
+                         256 * p.x_px_stride * 3 + (long long)p.K * 3 < (1ll << 31),
+                     AVS_E_UNSUPPORTED,
+                     "%s: an AVS_F16P8 input is taken by avs_conv2d_nhwc_bnstats for 1x1 / stride-1 convolutions on dense rows, "
+                     "cin a multiple of 32 (>= 64), the input row stride a multiple of 16", who);
+  }
+  // EPI_AFFINE: 256-row tiles, or 128-row ones for wide outputs when the caller asks (AVS_TILE_128) or the reduction is short
+  // (short reductions, K <= 128: three 128-row workgroups per CU overlap their loops and their epilogue traffic better
+  //  than two 256-row ones - l2.conv3 +5 %, l1.conv3 +2 %, bit-identical outputs)
+  if (p.affine) {
+    pl.tall = !(!narrow && (tile_mode == AVS_TILE_128 || (tile_mode == AVS_TILE_AUTO && p.K <= AVS_RULE_AFFINE_128_MAX_K)));
+    // the 128-row form exists on 64-byte reduction steps only: a longer reduction keeps the 256-row tile whatever the caller
+    // asks for (the variant is a tuning hint: results do not depend on it)
+    if (!pl.tall && (long long)p.K * 4 > g_rowb_threshold_bytes) pl.tall = true;
+  }
+  pl.tile_rows = p.tile_rows ? p.tile_rows : (pl.tall ? 256 : 128);
+  pl.tiles_m = ((long long)p.M + pl.tile_rows - 1) / pl.tile_rows;
+  AVS_PLAN_REQUIRE(pl.tiles_m * pl.tiles_n < (1ll << 31), AVS_E_SHAPE, "%s: too many tiles", who);
+  pl.grid = pl.tiles_m * pl.tiles_n;
+
+  // the per-tap bounds tests are only needed when a tap can leave the image
+  pl.spatial = !(p.ph == 0 && p.pw == 0 && (p.HoWo / p.Wo - 1) * p.sh + (p.K / (p.cin * p.KW)) - 1 < p.H &&
+                 (p.Wo - 1) * p.sw + p.KW - 1 < p.W);
+  // dense 1x1 / stride-1 input (and every plain GEMM): output row m reads input row m
+  pl.lin_stride = -1;
+  if (!pl.spatial && p.KW == 1 && p.K == p.cin && p.sh == 1 && p.sw == 1) {
+    if (p.HoWo == 1)
+      pl.lin_stride = p.x_img_stride;
+    else if (p.x_row_stride == (long long)p.Wo * p.x_px_stride && p.x_img_stride == (long long)p.HoWo * p.x_px_stride)
+      pl.lin_stride = p.x_px_stride;
+  }
+  if (p.tile_rows && dtype == AVS_F16X2) {
+    // a group of 193 .. 224 rows: the tile that fits it (local224.hip), unless the caller asks for the 256-row form
+    pl.local224 = igemm_h2_local224_ok(p, dtype, pl.lin_stride);
+    AVS_PLAN_REQUIRE(pl.local224 || p.cluster <= 1, AVS_E_UNSUPPORTED, "%s: the clustered form runs on the 224-row tile only", who);
+    AVS_PLAN_REQUIRE(pl.local224 || tile_mode != AVS_TILE_224, AVS_E_UNSUPPORTED,
+                     "%s: AVS_TILE_224 takes AVS_F16X2, groups of 193..224 rows, cout in multiples of 128, cin in multiples of 16", who);
+    if (pl.local224) return AVS_OK;
+  }
+
+  // igemm_kernel's arguments.  The epilogue: the compile-time forms, else the general one
+  pl.epi = EPI_ANY;
+  if (p.tile_rows)
+    pl.epi = EPI_BNLOCAL;
+  else if (p.affine)
+    pl.epi = EPI_AFFINE;
+  else if (p.bias_mode == AVS_BIAS_NONE && p.act == AVS_ACT_NONE && p.alpha == 1.0f)
+    pl.epi = stats ? EPI_STATS : EPI_PLAIN;
+  else if (brelu)
+    pl.epi = EPI_BRELU;
+  // 64-byte rows: short reductions, the 256-row tiles, and shapes whose channel count fits the scalar tap walk only
+  // at the 64-byte step (cin = 96, 160, 288 ... of Inception-v3): the cheaper staging is worth more than the longer step
+  const bool fast64_only = !(p.variant & AVS_STAGING_GENERIC) && p.cin % (64 / es) == 0 && p.cin % (128 / es) != 0 && p.K / p.cin <= 32;
+  const bool short_k = pl.tall || fast64_only || (long long)p.K * es <= g_rowb_threshold_bytes;
+  pl.rowb = short_k ? 64 : 128;
+  // the pipeline: 64-byte rows and at least three steps, else there is nothing to pipeline; the 256-row tiles are built on it
+  pl.pipe = pl.rowb == 64 && !pl.acc64 && g_pipe3 && p.K * es > 2 * pl.rowb;
+  pl.wr = pl.pipe && pl.tall ? 4 : 2;
+  pl.fastk = !pl.acc64 && igemm_fastk_ok(p, pl.lin_stride, es, pl.rowb / es, pl.bn);
+  // the shifted-row staging (one A fetch per channel block serves every tap) exists on the pipelined 256-row tiles with the
+  // scalar tap walk: bf16 and AVS_F16X2 3x3 / 1 / pad 1 under the statistics and tile-local BatchNorm epilogues, AVS_F16X2
+  // stride-1 "same" filters under bias + ReLU; the input affine rides in the AVS_F16X2 nine-tap statistics form only
+  if (pl.spatial && pl.pipe && pl.wr == 4 && pl.fastk && (es == 2 || pl.split == 2)) {
+    if (pl.epi == EPI_STATS || pl.epi == EPI_BNLOCAL)
+      pl.tap9 = igemm_tap9_ok(p, es);
+    else if (pl.epi == EPI_BRELU && pl.split == 2)
+      pl.tap9 = igemm_taps_ok(p);
+  }
+  pl.xin = in_affine && pl.tap9 && pl.split == 2 && pl.epi == EPI_STATS;
+  // an AVS_F16P8 input (validated above): the 1x1 statistics form with the A fragments rebuilt in registers
+  pl.ap8 = p.x_p8 && pl.split == 2 && pl.epi == EPI_STATS && !pl.spatial && pl.pipe && pl.fastk;
+  return AVS_OK;
+}
+#undef AVS_PLAN_REQUIRE
+
+// ---- igemm_run(): the plan's fields lifted to igemm_kernel's template arguments, one level per field; the `if constexpr`
+// gates say which instantiations exist (BN = 96: the AVS_F16X2 bias + ReLU form on the pipelined 256-row tiles only).  Every
+// level returns whether a kernel was launched: a plan that has no instantiation is an error of the rules, reported as
+// AVS_E_UNSUPPORTED - never a silent AVS_OK with an untouched output
 #define AVS_LAUNCH_RET(K)                                     \
   do {                                                        \
     hipLaunchKernelGGL(K, grid, dim3(256), 0, stream, p);     \
     return true;                                              \
   } while (0)
-template <int ES, int BN, bool ACC64, bool SP, int ROWB, bool PIPE, int WR, bool FK>
-static bool igemm_dispatch_epi4(int epi, dim3 grid, hipStream_t stream, const IgemmParams& p) {
-  if (p.in_scale) {   // the input-affine form exists as the AVS_F16X2 nine-tap convolution + statistics only
-    if constexpr (ES == 4 && !ACC64 && SP && ROWB == 64 && PIPE && WR == 4 && FK) {
-      if (p.split == 2 && epi == EPI_STATS && igemm_tap9_ok(p, ES))
-        AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_STATS, PIPE, WR, FK, 2, true, false, true>));
+template <int ES, int BN, bool ACC64, bool SP, int ROWB, bool PIPE, int WR, bool FK, int EPI, int SPLIT>
+static bool igemm_lift_staging(const IgemmPlan& pl, dim3 grid, hipStream_t stream, const IgemmParams& p) {
+  constexpr bool shifted = SP && ROWB == 64 && PIPE && WR == 4 && FK &&
+                           (SPLIT == 2 ? (EPI == EPI_STATS || EPI == EPI_BNLOCAL || EPI == EPI_BRELU)
+                                       : (ES == 2 && (EPI == EPI_STATS || EPI == EPI_BNLOCAL)));
+  if (pl.in_affine) {
+    if constexpr (shifted && SPLIT == 2 && EPI == EPI_STATS) {
+      if (pl.xin) AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI, PIPE, WR, FK, SPLIT, true, false, true>));
     }
     return false;
   }
-  if constexpr (ES == 2 && WR == 4) {
-    if constexpr (SP && ROWB == 64 && PIPE && FK) {   // bf16 3x3 / 1 layers: the nine-tap form
-      if ((epi == EPI_BNLOCAL || epi == EPI_STATS) && igemm_tap9_ok(p, ES)) {
-        if (epi == EPI_BNLOCAL)
-          AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_BNLOCAL, PIPE, WR, FK, 0, true>));
-        else
-          AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_STATS, PIPE, WR, FK, 0, true>));
+  if constexpr (shifted) {
+    if (pl.tap9) AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI, PIPE, WR, FK, SPLIT, true>));
+  }
+  if constexpr (SPLIT == 2 && EPI == EPI_STATS && !SP && ROWB == 64 && PIPE && FK) {
+    if (pl.ap8) AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI, PIPE, WR, FK, SPLIT, false, true>));
+  }
+  AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI, PIPE, WR, FK, SPLIT>));
+}
+
+#define AVS_LIFT_FORM(EPI, SPLIT) \
+  if (pl.epi == EPI) return igemm_lift_staging<ES, BN, ACC64, SP, ROWB, PIPE, WR, FK, EPI, SPLIT>(pl, grid, stream, p)
+template <int ES, int BN, bool ACC64, bool SP, int ROWB, bool PIPE, int WR, bool FK>
+static bool igemm_lift_form(const IgemmPlan& pl, dim3 grid, hipStream_t stream, const IgemmParams& p) {
+  if constexpr (BN == 96) {
+    if (pl.split == 2) AVS_LIFT_FORM(EPI_BRELU, 2);
+    return false;
+  } else {
+    if constexpr (ES == 2 && WR == 4) AVS_LIFT_FORM(EPI_BNLOCAL, 0);
+    if constexpr (ES == 4) {
+      if (pl.split == 2) {   // AVS_F16X2: operands stored as fp16 hi | lo runs, three fp16 MFMAs per product
+        AVS_LIFT_FORM(EPI_PLAIN, 2);
+        AVS_LIFT_FORM(EPI_STATS, 2);
+        AVS_LIFT_FORM(EPI_BRELU, 2);
+        if constexpr (WR == 4) AVS_LIFT_FORM(EPI_BNLOCAL, 2);
+        // the given-affine form: 1x1 shapes on the pipelined tiles, 256 rows or (wide outputs) 128
+        if constexpr (!SP && ROWB == 64 && PIPE && (WR == 4 || BN == 128)) AVS_LIFT_FORM(EPI_AFFINE, 2);
+        return false;
+      }
+      if (pl.split == 1 || WR == 4) {   // AVS_F32_SPLIT: the same tiles, products as three bf16 MFMAs (WR = 4 exists for it only)
+        AVS_LIFT_FORM(EPI_PLAIN, 1);
+        AVS_LIFT_FORM(EPI_STATS, 1);
+        AVS_LIFT_FORM(EPI_BRELU, 1);
+        if constexpr (WR == 2) return igemm_lift_staging<ES, BN, ACC64, SP, ROWB, PIPE, WR, FK, EPI_ANY, 1>(pl, grid, stream, p);
       }
     }
-    if (epi == EPI_BNLOCAL) {
-      AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_BNLOCAL, PIPE, WR, FK>));
+    if constexpr (!(ES == 4 && WR == 4)) {   // (fp32 on 256-row tiles exists as fp32-split only: handled above)
+      AVS_LIFT_FORM(EPI_PLAIN, 0);
+      AVS_LIFT_FORM(EPI_STATS, 0);
+      AVS_LIFT_FORM(EPI_BRELU, 0);
+      if constexpr (WR == 2) return igemm_lift_staging<ES, BN, ACC64, SP, ROWB, PIPE, WR, FK, EPI_ANY, 0>(pl, grid, stream, p);
     }
+    return false;
   }
-  if constexpr (ES == 4 && !ACC64) {
-    if (p.split == 2) {         // AVS_F16X2: operands stored as fp16 hi | lo runs, three fp16 MFMAs per product
-      if (epi == EPI_PLAIN)
-        AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_PLAIN, PIPE, WR, FK, 2>));
-      else if (epi == EPI_STATS) {
-        if constexpr (SP && ROWB == 64 && PIPE && WR == 4 && FK) {
-          if (igemm_tap9_ok(p, ES)) {   // 3x3 / 1 / pad 1 on a dense input: one A fetch per channel block serves all nine taps
-            AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_STATS, PIPE, WR, FK, 2, true>));
-          }
-        }
-        if constexpr (!SP && ROWB == 64 && PIPE && FK) {
-          if (p.x_p8) {   // AVS_F16P8 input (validated by igemm_launch): A fragments fetched into registers
-            AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_STATS, PIPE, WR, FK, 2, false, true>));
-          }
-        }
-        AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_STATS, PIPE, WR, FK, 2>));
-      } else if (epi == EPI_BRELU) {
-        if constexpr (SP && ROWB == 64 && PIPE && WR == 4 && FK) {
-          if (igemm_taps_ok(p)) {   // stride-1 "same" filters: one A fetch per channel block serves every tap
-            AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_BRELU, PIPE, WR, FK, 2, true>));
-          }
-        }
-        AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_BRELU, PIPE, WR, FK, 2>));
-      } else if constexpr (WR == 4) {
-        if (epi == EPI_BNLOCAL) {
-          if constexpr (SP && ROWB == 64 && PIPE && FK) {
-            if (igemm_tap9_ok(p, ES)) {
-              AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_BNLOCAL, PIPE, WR, FK, 2, true>));
-            }
-          }
-          AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_BNLOCAL, PIPE, WR, FK, 2>));
-        }
-        if constexpr (!SP && ROWB == 64 && PIPE) {   // (the launcher only sends 1x1 shapes on the pipelined 256-row tiles here)
-          if (epi == EPI_AFFINE)
-            AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_AFFINE, PIPE, WR, FK, 2>));
-        }
-      } else if constexpr (!SP && ROWB == 64 && PIPE && BN == 128) {   // AVS_TILE_128: the given-affine form on 128-row tiles
-        if (epi == EPI_AFFINE)
-          AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_AFFINE, PIPE, WR, FK, 2>));
-      }
-      return false;
-    }
-    if (p.split || WR == 4) {   // AVS_F32_SPLIT: the same tiles, products as three bf16 MFMAs (WR = 4 exists for it only)
-      if (epi == EPI_PLAIN)
-        AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_PLAIN, PIPE, WR, FK, 1>));
-      else if (epi == EPI_STATS)
-        AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_STATS, PIPE, WR, FK, 1>));
-      else if (epi == EPI_BRELU)
-        AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_BRELU, PIPE, WR, FK, 1>));
-      else if constexpr (WR == 2)
-        AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_ANY, PIPE, WR, FK, 1>));
-    }
-  }
-  if constexpr (!(ES == 4 && WR == 4)) {   // (fp32 on 256-row tiles exists as fp32-split only: handled above)
-    if (epi == EPI_PLAIN)
-      AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_PLAIN, PIPE, WR, FK>));
-    else if (epi == EPI_STATS)
-      AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_STATS, PIPE, WR, FK>));
-    else if (epi == EPI_BRELU)
-      AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_BRELU, PIPE, WR, FK>));
-    else if constexpr (WR == 2)
-      AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_ANY, PIPE, WR, FK>));
-  }
-  return false;
 }
-
-
-// FASTK (the scalar tap walk over buffer_load ... lds): cin a whole number of reduction steps of bke elements, at most 32
-// taps, and the buffer window - a tile's rows (at most 256, spread over whole images) plus the tap walk - below 2 GiB
-static bool igemm_fastk_ok(const IgemmParams& p, int es, int bke, int bn) {
-  const long long rows = 256;
-  long long extent;
-  if (p.lin_stride >= 0)
-    extent = rows * p.lin_stride + p.K;
-  else
-    extent = (rows / p.HoWo + 2) * p.x_img_stride + (long long)(p.K / (p.cin * p.KW) + p.ph) * p.x_row_stride +
-             (long long)(p.KW + p.pw) * p.x_px_stride + p.cin;
-  const bool window_ok = extent * es < (1ll << 31) && (long long)bn * p.ldb * es + (long long)p.K * es < (1ll << 31) &&
-                         p.x_img_stride >= 0 && p.x_row_stride >= 0 && p.x_px_stride >= 0;
-  return !(p.variant & AVS_STAGING_GENERIC) && window_ok && p.cin % bke == 0 && p.K % bke == 0 && p.K / p.cin <= 32 &&
-         p.K % p.cin == 0;
-}
-
-template <int ES, int BN, bool ACC64, bool SP, int ROWB, bool PIPE, int WR>
-static bool igemm_dispatch_epi3(int epi, dim3 grid, hipStream_t stream, const IgemmParams& p) {
-  if (igemm_fastk_ok(p, ES, ROWB / ES, BN))
-    return igemm_dispatch_epi4<ES, BN, ACC64, SP, ROWB, PIPE, WR, true>(epi, grid, stream, p);
-  else
-    return igemm_dispatch_epi4<ES, BN, ACC64, SP, ROWB, PIPE, WR, false>(epi, grid, stream, p);
-}
-
-// AVS_F16X2 bias + ReLU on 256 x 96 tiles (igemm_launch's rule: cout = 96, 160, 192, 288 ... with enough rows)
-static bool igemm_dispatch_brelu96(bool spatial, dim3 grid, hipStream_t stream, const IgemmParams& p) {
-#ifdef AVS_STUDY
-  const_cast<IgemmParams&>(p).debug = g_debug_flags;
-#endif
-  const bool fk = igemm_fastk_ok(p, 4, 16, 96);
-  if (spatial) {
-    if (fk && igemm_taps_ok(p)) AVS_LAUNCH_RET((igemm_kernel<4, 96, false, true, 64, EPI_BRELU, true, 4, true, 2, true>));
-    if (fk) AVS_LAUNCH_RET((igemm_kernel<4, 96, false, true, 64, EPI_BRELU, true, 4, true, 2>));
-    AVS_LAUNCH_RET((igemm_kernel<4, 96, false, true, 64, EPI_BRELU, true, 4, false, 2>));
-  }
-  if (fk) AVS_LAUNCH_RET((igemm_kernel<4, 96, false, false, 64, EPI_BRELU, true, 4, true, 2>));
-  AVS_LAUNCH_RET((igemm_kernel<4, 96, false, false, 64, EPI_BRELU, true, 4, false, 2>));
-}
+#undef AVS_LIFT_FORM
 
 template <int ES, int BN, bool ACC64, bool SP, int ROWB, bool PIPE>
-static bool igemm_dispatch_epi2(int epi, dim3 grid, hipStream_t stream, const IgemmParams& p) {
-  if constexpr (ACC64) {
+static bool igemm_lift_tile(const IgemmPlan& pl, dim3 grid, hipStream_t stream, const IgemmParams& p) {
+  if constexpr (ACC64) {   // fp64 slice accumulation: the general epilogue on the classic 128-row walk
     AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI_ANY, false>));
   } else {
     if constexpr (ROWB == 64 && PIPE) {
-      if (p.tall) {  // igemm_launch only sets it for the epilogue forms compiled at WR = 4 (bf16; fp32 only as fp32-split)
-        return igemm_dispatch_epi3<ES, BN, ACC64, SP, ROWB, PIPE, 4>(epi, grid, stream, p);
-      }
+      if (pl.wr == 4)
+        return pl.fastk ? igemm_lift_form<ES, BN, ACC64, SP, ROWB, PIPE, 4, true>(pl, grid, stream, p)
+                        : igemm_lift_form<ES, BN, ACC64, SP, ROWB, PIPE, 4, false>(pl, grid, stream, p);
     }
-    return igemm_dispatch_epi3<ES, BN, ACC64, SP, ROWB, PIPE, 2>(epi, grid, stream, p);
+    if constexpr (BN != 96) {
+      if (pl.wr == 2)
+        return pl.fastk ? igemm_lift_form<ES, BN, ACC64, SP, ROWB, PIPE, 2, true>(pl, grid, stream, p)
+                        : igemm_lift_form<ES, BN, ACC64, SP, ROWB, PIPE, 2, false>(pl, grid, stream, p);
+    }
+    return false;
   }
 }
 
 template <int ES, int BN, bool ACC64, bool SP, int ROWB>
-static bool igemm_dispatch_epi(int epi, dim3 grid, hipStream_t stream, const IgemmParams& p) {
+static bool igemm_lift_pipe(const IgemmPlan& pl, dim3 grid, hipStream_t stream, const IgemmParams& p) {
   if constexpr (ROWB == 64 && !ACC64) {
-    if (g_pipe3 && p.K * ES > 2 * ROWB) {  // at least three steps, else there is nothing to pipeline
-      return igemm_dispatch_epi2<ES, BN, ACC64, SP, ROWB, true>(epi, grid, stream, p);
-    }
+    if (pl.pipe) return igemm_lift_tile<ES, BN, ACC64, SP, ROWB, true>(pl, grid, stream, p);
   }
-  return igemm_dispatch_epi2<ES, BN, ACC64, SP, ROWB, false>(epi, grid, stream, p);
+  if constexpr (BN != 96) {
+    if (!pl.pipe) return igemm_lift_tile<ES, BN, ACC64, SP, ROWB, false>(pl, grid, stream, p);
+  }
+  return false;
 }
 
 template <int ES, int BN, bool ACC64>
-static bool igemm_dispatch(bool spatial, dim3 grid, hipStream_t stream, const IgemmParams& p) {
-#ifdef AVS_STUDY
-  const_cast<IgemmParams&>(p).debug = g_debug_flags;
-#endif
-  // 64-byte rows: short reductions, the 256-row tiles, and shapes whose channel count fits the scalar tap walk only
-  // at the 64-byte step (cin = 96, 160, 288 ... of Inception-v3): the cheaper staging is worth more than the longer step
-  const bool fast64_only = !(p.variant & AVS_STAGING_GENERIC) && p.cin % (64 / ES) == 0 && p.cin % (128 / ES) != 0 && p.K / p.cin <= 32;
-  const bool short_k = p.tall || fast64_only || (long long)p.K * ES <= g_rowb_threshold_bytes;
-  int epi = EPI_ANY;
-  if (p.tile_rows)
-    epi = EPI_BNLOCAL;
-  else if (p.affine)
-    epi = EPI_AFFINE;
-  else if (p.bias_mode == AVS_BIAS_NONE && p.act == AVS_ACT_NONE && p.alpha == 1.0f)
-    epi = p.stat_part ? EPI_STATS : EPI_PLAIN;
-  else if (p.bias_mode == AVS_BIAS_COL && p.act == AVS_ACT_RELU && p.alpha == 1.0f && !p.stat_part)
-    epi = EPI_BRELU;
-  if (short_k) {
-    if (spatial)
-      return igemm_dispatch_epi<ES, BN, ACC64, true, 64>(epi, grid, stream, p);
-    else
-      return igemm_dispatch_epi<ES, BN, ACC64, false, 64>(epi, grid, stream, p);
-  } else {
-    if (spatial)
-      return igemm_dispatch_epi<ES, BN, ACC64, true, 128>(epi, grid, stream, p);
-    else
-      return igemm_dispatch_epi<ES, BN, ACC64, false, 128>(epi, grid, stream, p);
+static bool igemm_lift(const IgemmPlan& pl, dim3 grid, hipStream_t stream, const IgemmParams& p) {
+  if (pl.es != ES || pl.bn != BN || pl.acc64 != ACC64) return false;
+  if (pl.rowb == 64)
+    return pl.spatial ? igemm_lift_pipe<ES, BN, ACC64, true, 64>(pl, grid, stream, p)
+                      : igemm_lift_pipe<ES, BN, ACC64, false, 64>(pl, grid, stream, p);
+  if constexpr (BN != 96) {
+    if (pl.rowb == 128)
+      return pl.spatial ? igemm_lift_pipe<ES, BN, ACC64, true, 128>(pl, grid, stream, p)
+                        : igemm_lift_pipe<ES, BN, ACC64, false, 128>(pl, grid, stream, p);
   }
+  return false;
 }
 
-// plan_only: validate the shape and choose the tile (p.tall, p.tiles_n, *tiles_m_out) as for a launch, launch nothing
-static int igemm_launch(int dtype, IgemmParams& p, int batch, hipStream_t stream, const char* who,
-                        bool plan_only = false, long long* tiles_m_out = nullptr) {
-  const int es = dtype == AVS_BF16 ? 2 : 4;
-  p.split = dtype == AVS_F32_SPLIT ? 1 : (dtype == AVS_F16X2 ? 2 : 0);
-  const int ce = dtype == AVS_F16X2 ? 8 : 16 / es;   // AVS_F16X2: whole hi | lo runs of 8 slots
-  AVS_REQUIRE(dtype == AVS_F32 || dtype == AVS_BF16 || dtype == AVS_F32_ACC64 || dtype == AVS_F32_SPLIT ||
-                  dtype == AVS_F16X2, AVS_E_ARG, "%s: bad dtype %d", who, dtype);
-  if (dtype == AVS_F16X2) {
-    const bool fixed = p.alpha == 1.0f &&
-                       ((p.bias_mode == AVS_BIAS_NONE && (p.act == AVS_ACT_NONE || p.tile_rows || p.affine)) ||
-                        (p.bias_mode == AVS_BIAS_COL && p.act == AVS_ACT_RELU && !p.stat_part && !p.tile_rows && !p.affine));
-    AVS_REQUIRE(fixed, AVS_E_UNSUPPORTED,
-                "%s: AVS_F16X2 takes alpha = 1 and either no bias / activation (or a BatchNorm form) or bias per column + ReLU", who);
-    AVS_REQUIRE(p.N % 8 == 0 && p.ldc % 8 == 0 && (p.sC % 8) == 0, AVS_E_SHAPE,
-                "%s: AVS_F16X2 needs cout and the output strides in multiples of 8 slots", who);
-    AVS_REQUIRE(plan_only || ((((uintptr_t)p.x) | ((uintptr_t)p.w) | ((uintptr_t)p.y)) & 31u) == 0, AVS_E_ALIGN,
+// The checks that need the operands themselves, then the launch.  The documented order of checks interleaves them with the
+// plan's: those the plan had passed when it ended (pl.operand_checks) come before its own verdict, so the status is that
+// of the first failing check in the one order whichever side makes it.
+static int igemm_run(const IgemmPlan& pl, IgemmParams& p, hipStream_t stream, const char* who) {
+  if (pl.operand_checks >= 1 && pl.dtype == AVS_F16X2)
+    AVS_REQUIRE(((((uintptr_t)p.x) | ((uintptr_t)p.w) | ((uintptr_t)p.y)) & 31u) == 0, AVS_E_ALIGN,
                 "%s: AVS_F16X2 operands must be 32-byte aligned", who);
+  if (pl.operand_checks >= 2) {
+    AVS_REQUIRE(p.x && p.w && p.y, AVS_E_ARG, "%s: null operand", who);
+    AVS_REQUIRE(p.bias_mode == AVS_BIAS_NONE || p.bias, AVS_E_ARG, "%s: bias mode %d without bias", who, p.bias_mode);
   }
-  AVS_REQUIRE(p.M >= 0 && p.N > 0 && p.K > 0 && batch > 0, AVS_E_SHAPE, "%s: bad sizes M=%d N=%d K=%d batch=%d", who,
-              p.M, p.N, p.K, batch);
-  if (p.M == 0) return AVS_OK;
-  AVS_REQUIRE(plan_only || (p.x && p.w && p.y), AVS_E_ARG, "%s: null operand", who);
-  AVS_REQUIRE(p.bias_mode == AVS_BIAS_NONE || p.bias, AVS_E_ARG, "%s: bias mode %d without bias", who, p.bias_mode);
-  AVS_REQUIRE(p.cin % ce == 0 && p.K % ce == 0, AVS_E_SHAPE,
-              "%s: cin=%d / K=%d must be multiples of %d elements (16 bytes)", who, p.cin, p.K, ce);
-  AVS_REQUIRE(plan_only || (avs_aligned16(p.x) && avs_aligned16(p.w)), AVS_E_ALIGN, "%s: x / w must be 16-byte aligned",
-              who);
-  AVS_REQUIRE((p.x_img_stride * es) % (ce * es) == 0 && (p.x_row_stride * es) % (ce * es) == 0 &&
-                  (p.x_px_stride * es) % (ce * es) == 0 && (p.ldb * es) % (ce * es) == 0 && (p.sA * es) % (ce * es) == 0 &&
-                  (p.sB * es) % (ce * es) == 0,
-              AVS_E_ALIGN, "%s: strides must be multiples of %d bytes", who, ce * es);
-  if (p.nsplit > 0) {                                             // two destinations: each row stride covers its own columns
-    AVS_REQUIRE(p.ldc >= p.nsplit && p.ldc2 >= p.N - p.nsplit, AVS_E_SHAPE,
-                "%s: output row strides %lld / %lld < the %d / %d columns of the two destinations", who, p.ldc, p.ldc2,
-                p.nsplit, p.N - p.nsplit);
-  } else {
-    AVS_REQUIRE(p.ldc >= p.N, AVS_E_SHAPE, "%s: output row stride %lld < N=%d", who, p.ldc, p.N);
+  if (pl.operand_checks >= 3)
+    AVS_REQUIRE(avs_aligned16(p.x) && avs_aligned16(p.w), AVS_E_ALIGN, "%s: x / w must be 16-byte aligned", who);
+  if (pl.status != AVS_OK) return pl.status;
+  if (pl.grid == 0) return AVS_OK;
+  p.split = pl.split;
+  p.tall = pl.tall;
+  p.tiles_n = pl.tiles_n;
+  p.lin_stride = pl.lin_stride;
+#ifdef AVS_STUDY
+  p.debug = g_debug_flags;
+#endif
+  const dim3 grid((unsigned)pl.grid, 1, (unsigned)pl.batch);
+  if (pl.local224) {
+    igemm_h2_local224_launch(p, pl.spatial, grid, stream);
+    AVS_CHECK_LAUNCH(who);
+    return AVS_OK;
   }
-  AVS_REQUIRE(batch <= 65535, AVS_E_SHAPE, "%s: batch %d > 65535", who, batch);
-
-  // exact fp32 with few tiles (the scorer's linear layers and their gradients: 1800 rows x 512 .. 2048 columns = 16 .. 240
-  // tiles of 128 x 128 on 256 CUs x 3 workgroups): 64-wide column tiles double the workgroups; the same sums in the same order
-  const bool few_f32 = dtype == AVS_F32 && batch == 1 && !p.stat_part && !p.tile_rows && !p.affine &&
-                       (((long long)p.M + 127) / 128) * ((p.N + 127) / 128) < 256;
-  const bool narrow = p.N <= 64 || dtype == AVS_F32_ACC64 || few_f32;
-  int bn = narrow ? 64 : 128;
-  p.tiles_n = (p.N + bn - 1) / bn;
-  // AVS_F16X2 bias + ReLU (Inception-v3's folded-BatchNorm convolutions): cout = 96, 160, 192, 288 ... leave a 128-wide
-  // column tile 25 - 37 % empty; 96-wide tiles on the 256-row form when they save at least 15 % of the padded width and the
-  // 256-row rule below holds for them (a tuning choice: the outputs do not depend on it; AVS_TILE_128 keeps the 128-row tiles)
-  bool wide96 = false;
-  if (dtype == AVS_F16X2 && !narrow && p.alpha == 1.0f && p.bias_mode == AVS_BIAS_COL && p.act == AVS_ACT_RELU && !p.stat_part &&
-      !p.tile_rows && !p.affine && batch == 1 && g_pipe3 && (long long)p.K * 4 >= g_tall_min_k_bytes &&
-      ((p.variant & 3) == AVS_TILE_AUTO || (p.variant & 3) == AVS_TILE_256)) {
-    const int t96 = (p.N + 95) / 96;
-    const long long tall_tiles96 = ((long long)p.M + 255) / 256 * t96;
-    if (t96 * 96 * 100 <= p.tiles_n * 128 * 85 && ((p.variant & 3) == AVS_TILE_256 || tall_tiles96 >= g_tall_min_tiles)) {
-      wide96 = true;
-      bn = 96;
-      p.tiles_n = t96;
-    }
-  }
-  // 256-row tiles (WR = 4): bf16, the compile-time epilogue forms, a reduction of at least three 64-byte steps (the
-  // variants are built on the 3-buffer pipeline), and enough rows that the grid still fills the chip several times
-  p.tall = 0;
-  {
-    const bool fixed_epi = p.alpha == 1.0f &&
-                           ((p.bias_mode == AVS_BIAS_NONE && p.act == AVS_ACT_NONE) ||
-                            (p.bias_mode == AVS_BIAS_COL && p.act == AVS_ACT_RELU && !p.stat_part));
-    const bool can = (dtype == AVS_BF16 || dtype == AVS_F32_SPLIT || dtype == AVS_F16X2) && fixed_epi && g_pipe3 &&
-                     (long long)p.K * es > 128 && batch == 1;
-    const long long tall_tiles = ((long long)p.M + 255) / 256 * p.tiles_n;
-    const int tile_mode = p.variant & 3;   // AVS_TILE_AUTO: by rule; AVS_TILE_128: never; AVS_TILE_256: wherever it exists
-    AVS_REQUIRE(tile_mode != AVS_TILE_224 || p.tile_rows, AVS_E_UNSUPPORTED,
-                "%s: AVS_TILE_224 is a tile of the tile-local BatchNorm form (avs_conv2d_nhwc_bnlocal)", who);
-    if (can && (tile_mode == AVS_TILE_256 || (tile_mode == AVS_TILE_AUTO && tall_tiles >= g_tall_min_tiles &&
-                                              (narrow || (long long)p.K * es >= g_tall_min_k_bytes))))
-      p.tall = 1;
-    if (wide96) p.tall = 1;
-  }
-  // EPI_BNLOCAL (validated by bnlocal_plan): 256-row tiles at a pitch of tile_rows; EPI_AFFINE: 256-row tiles, or 128-row
-  // ones for wide outputs when the caller asks (AVS_TILE_128) or the reduction is short
-  // (short reductions, K <= 128: three 128-row workgroups per CU overlap their loops and their epilogue traffic better
-  //  than two 256-row ones - l2.conv3 +5 %, l1.conv3 +2 %, bit-identical outputs)
-  if (p.tile_rows) p.tall = 1;
-  // AVS_F16P8 operands: the input of the 1x1 convolution + statistics form on the 256-row tiles (A fragments in registers),
-  // the output / residual of the given-affine form
-  AVS_REQUIRE(!(p.y_p8 || p.res_p8) || (p.affine && p.N % 16 == 0 && p.ldc % 16 == 0 && p.ldr % 16 == 0), AVS_E_UNSUPPORTED,
-              "%s: an AVS_F16P8 output / residual is taken by avs_conv2d_nhwc_affine (cout and row strides in multiples of 16)", who);
-  if (p.x_p8) {
-    AVS_REQUIRE(p.stat_part && !p.tile_rows && !p.affine && batch == 1 && g_pipe3 && !(p.variant & AVS_STAGING_GENERIC) &&
-                    (p.tall || (long long)p.K * 4 <= g_rowb_threshold_bytes) &&   // (64-byte reduction steps)
-                    p.KW == 1 && p.K == p.cin && p.K % 32 == 0 && p.K >= 64 &&
-                    p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 && p.x_row_stride == (long long)p.Wo * p.x_px_stride &&
-                    p.x_img_stride == (long long)p.HoWo * p.x_px_stride && p.x_px_stride % 16 == 0 &&
-                    256 * p.x_px_stride * 3 + (long long)p.K * 3 < (1ll << 31),
-                AVS_E_UNSUPPORTED,
-                "%s: an AVS_F16P8 input is taken by avs_conv2d_nhwc_bnstats for 1x1 / stride-1 convolutions on dense rows, "
-                "cin a multiple of 32 (>= 64), the input row stride a multiple of 16", who);
-  }
-  if (p.affine) {
-    const int tile_mode = p.variant & 3;
-    p.tall = (!narrow && (tile_mode == AVS_TILE_128 || (tile_mode == AVS_TILE_AUTO && p.K <= AVS_RULE_AFFINE_128_MAX_K))) ? 0 : 1;
-    // the 128-row form exists on 64-byte reduction steps only: a longer reduction keeps the 256-row tile whatever the caller
-    // asks for (the variant is a tuning hint: results do not depend on it)
-    if (!p.tall && (long long)p.K * 4 > g_rowb_threshold_bytes) p.tall = 1;
-  }
-  const int tile_rows = p.tile_rows ? p.tile_rows : (p.tall ? 256 : 128);
-  const long long tiles_m = ((long long)p.M + tile_rows - 1) / tile_rows;
-  const long long total = tiles_m * p.tiles_n;
-  AVS_REQUIRE(total < (1ll << 31), AVS_E_SHAPE, "%s: too many tiles", who);
-  if (tiles_m_out) *tiles_m_out = tiles_m;
-  if (plan_only) return AVS_OK;
-  // the per-tap bounds tests are only needed when a tap can leave the image
-  const bool spatial = !(p.ph == 0 && p.pw == 0 && (p.HoWo / p.Wo - 1) * p.sh + (p.K / (p.cin * p.KW)) - 1 < p.H &&
-                         (p.Wo - 1) * p.sw + p.KW - 1 < p.W);
-  // dense 1x1 / stride-1 input (and every plain GEMM): output row m reads input row m
-  p.lin_stride = -1;
-  if (!spatial && p.KW == 1 && p.K == p.cin && p.sh == 1 && p.sw == 1) {
-    if (p.HoWo == 1)
-      p.lin_stride = p.x_img_stride;
-    else if (p.x_row_stride == (long long)p.Wo * p.x_px_stride && p.x_img_stride == (long long)p.HoWo * p.x_px_stride)
-      p.lin_stride = p.x_px_stride;
-  }
-  dim3 grid((unsigned)total, 1, (unsigned)batch);
-  if (p.tile_rows && dtype == AVS_F16X2) {
-    // a group of 193 .. 224 rows: the tile that fits it (local224.hip), unless the caller asks for the 256-row form
-    const bool fits = igemm_h2_local224_ok(p, dtype);
-    AVS_REQUIRE(fits || p.cluster <= 1, AVS_E_UNSUPPORTED, "%s: the clustered form runs on the 224-row tile only", who);
-    AVS_REQUIRE(fits || (p.variant & 3) != AVS_TILE_224, AVS_E_UNSUPPORTED,
-                "%s: AVS_TILE_224 takes AVS_F16X2, groups of 193..224 rows, cout in multiples of 128, cin in multiples of 16", who);
-    if (fits) {
-      igemm_h2_local224_launch(p, spatial, grid, stream);
-      AVS_CHECK_LAUNCH(who);
-      return AVS_OK;
-    }
-  }
-  bool launched;
-  if (wide96) {
-    launched = igemm_dispatch_brelu96(spatial, grid, stream, p);
-  } else if (dtype == AVS_BF16) {
-    launched = narrow ? igemm_dispatch<2, 64, false>(spatial, grid, stream, p) : igemm_dispatch<2, 128, false>(spatial, grid, stream, p);
-  } else if (dtype == AVS_F32_ACC64) {
-    launched = igemm_dispatch<4, 64, true>(spatial, grid, stream, p);
-  } else {
-    launched = narrow ? igemm_dispatch<4, 64, false>(spatial, grid, stream, p) : igemm_dispatch<4, 128, false>(spatial, grid, stream, p);
-  }
+  const bool launched = igemm_lift<2, 64, false>(pl, grid, stream, p) || igemm_lift<2, 128, false>(pl, grid, stream, p) ||
+                        igemm_lift<4, 64, true>(pl, grid, stream, p) || igemm_lift<4, 64, false>(pl, grid, stream, p) ||
+                        igemm_lift<4, 96, false>(pl, grid, stream, p) || igemm_lift<4, 128, false>(pl, grid, stream, p);
   AVS_REQUIRE(launched, AVS_E_UNSUPPORTED,
-              "%s: no kernel for this combination (dtype %d, %s tile, K = %d, N = %d, variant %d, %s%s%s): nothing was launched", who,
-              dtype, p.tall ? "256-row" : "128-row", p.K, p.N, p.variant, p.affine ? "given-affine " : "", p.tile_rows ? "tile-local " : "",
-              p.stat_part ? "statistics" : "");
+              "%s: no kernel for this plan (dtype %d, %d x %d tile, K = %d, N = %d, variant %d, %d-byte steps, epilogue %d, pipe %d, "
+              "fastk %d, tap9 %d, ap8 %d, xin %d): nothing was launched", who, pl.dtype, pl.wr * 64, pl.bn, p.K, p.N, p.variant,
+              pl.rowb, pl.epi, pl.pipe, pl.fastk, pl.tap9, pl.ap8, pl.in_affine);
   AVS_CHECK_LAUNCH(who);
   return AVS_OK;
 }
 
-static int conv_fill_params(const avs_conv_desc* d, const void* d_x, const void* d_w, const float* d_bias, void* d_y,
-                            IgemmParams& p, const char* who) {
+static int igemm_launch(int dtype, IgemmParams& p, int batch, hipStream_t stream, const char* who) {
+  IgemmPlan pl;
+  igemm_plan(dtype, p, batch, p.stat_part != nullptr, p.in_scale != nullptr, who, pl);
+  return igemm_run(pl, p, stream, who);
+}
+
+// descriptor -> geometry and options, with every check on them; no operand (has_bias: a bias per column will be given)
+static int conv_geometry(const avs_conv_desc* d, bool has_bias, IgemmParams& p, const char* who) {
   AVS_REQUIRE(d != nullptr, AVS_E_ARG, "%s: null descriptor", who);
   AVS_REQUIRE(d->n >= 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->kh > 0 && d->kw > 0 && d->sh > 0 && d->sw > 0 &&
                   d->ph >= 0 && d->pw >= 0 && d->ho > 0 && d->wo > 0 && d->cout > 0,
@@ -2077,10 +2070,6 @@ static int conv_fill_params(const avs_conv_desc* d, const void* d_x, const void*
               AVS_E_SHAPE, "%s: output extent %dx%d exceeds what input %dx%d allows", who, d->ho, d->wo, d->h, d->w);
   const long long rows = (long long)d->n * d->ho * d->wo;
   AVS_REQUIRE(rows < (1ll << 31), AVS_E_SHAPE, "%s: %lld output pixels exceed int32", who, rows);
-  p.x = (const char*)d_x;
-  p.w = (const char*)d_w;
-  p.y = (char*)d_y;
-  p.bias = d_bias;
   p.M = (int)rows;
   p.N = d->cout;
   p.K = d->kh * d->kw * d->cin;
@@ -2114,16 +2103,24 @@ static int conv_fill_params(const avs_conv_desc* d, const void* d_x, const void*
   p.ldc = d->y_px_stride;
   p.alpha = d->alpha;
   p.act = d->act;
-  p.bias_mode = d_bias ? AVS_BIAS_COL : AVS_BIAS_NONE;
+  p.bias_mode = has_bias ? AVS_BIAS_COL : AVS_BIAS_NONE;
   AVS_REQUIRE(p.ldb >= p.K, AVS_E_SHAPE, "%s: w_row_stride %lld < kh*kw*cin=%d", who, p.ldb, p.K);
   return AVS_OK;
+}
+
+static void conv_operands(IgemmParams& p, const void* d_x, const void* d_w, const float* d_bias, void* d_y) {
+  p.x = (const char*)d_x;
+  p.w = (const char*)d_w;
+  p.y = (char*)d_y;
+  p.bias = d_bias;
 }
 
 extern "C" int avs_conv2d_nhwc(const avs_conv_desc* d, const void* d_x, const void* d_w, const float* d_bias,
                                void* d_y, avs_stream_t stream) {
   IgemmParams p{};
-  int st = conv_fill_params(d, d_x, d_w, d_bias, d_y, p, "avs_conv2d_nhwc");
+  int st = conv_geometry(d, d_bias != nullptr, p, "avs_conv2d_nhwc");
   if (st != AVS_OK) return st;
+  conv_operands(p, d_x, d_w, d_bias, d_y);
   return igemm_launch(d->dtype, p, 1, (hipStream_t)stream, "avs_conv2d_nhwc");
 }
 
@@ -2135,8 +2132,9 @@ extern "C" int avs_conv2d_nhwc_split(const avs_conv_desc* d, const void* d_x, co
                                      avs_stream_t stream) {
   const char* who = "avs_conv2d_nhwc_split";
   IgemmParams p{};
-  int st = conv_fill_params(d, d_x, d_w, d_bias, d_y, p, who);
+  int st = conv_geometry(d, d_bias != nullptr, p, who);
   if (st != AVS_OK) return st;
+  conv_operands(p, d_x, d_w, d_bias, d_y);
   AVS_REQUIRE(d->dtype == AVS_F16X2, AVS_E_UNSUPPORTED, "%s: built for AVS_F16X2", who);
   AVS_REQUIRE(n_split > 0 && n_split < p.N && n_split % 8 == 0 && n_split <= p.ldc && y2_px_stride >= p.N - n_split &&
                   y2_px_stride % 8 == 0,
@@ -2200,7 +2198,8 @@ __global__ __launch_bounds__(256) void bn_fold_kernel(const float* __restrict__ 
   }
 }
 
-static int bnstats_plan(const avs_conv_desc* d, int64_t rpg, IgemmParams& p, int64_t* ws_bytes, int* tile_rows,
+// the statistics-epilogue plan of a convolution, and the workspace its row tiles' slots need
+static int bnstats_plan(const avs_conv_desc* d, int64_t rpg, bool in_affine, IgemmParams& p, IgemmPlan& pl, int64_t* ws_bytes,
                         const char* who) {
   AVS_REQUIRE(d != nullptr && (d->dtype == AVS_BF16 || d->dtype == AVS_F32 || d->dtype == AVS_F32_SPLIT ||
                                d->dtype == AVS_F16X2), AVS_E_ARG, "%s: bf16 / fp32 / f16x2 only", who);
@@ -2209,26 +2208,22 @@ static int bnstats_plan(const avs_conv_desc* d, int64_t rpg, IgemmParams& p, int
   AVS_REQUIRE(rpg >= STATS_MIN_GROUP_ROWS, AVS_E_UNSUPPORTED,
               "%s: groups of fewer than %d rows take the separate statistics pass (avs_bn_batch_stats)", who,
               STATS_MIN_GROUP_ROWS);
-  long long tiles_m = 0;
-  p.stat_part = reinterpret_cast<float*>(16);  // selects EPI_STATS in the plan (same tile choice as the launch)
-  const int st = igemm_launch(d->dtype, p, 1, nullptr, who, true, &tiles_m);
-  p.stat_part = nullptr;
+  const int st = igemm_plan(d->dtype, p, 1, true, in_affine, who, pl);
   if (st != AVS_OK) return st;
-  *tile_rows = p.tall ? 256 : 128;
-  p.stat_slots = (int)((*tile_rows + rpg - 2) / rpg + 1);
-  *ws_bytes = (int64_t)((tiles_m * p.stat_slots * 2 * p.N * 4 + 255) / 256 * 256);
+  p.stat_slots = (int)((pl.tile_rows + rpg - 2) / rpg + 1);
+  *ws_bytes = (int64_t)((pl.tiles_m * p.stat_slots * 2 * p.N * 4 + 255) / 256 * 256);
   return AVS_OK;
 }
 
 extern "C" int64_t avs_conv2d_bnstats_workspace_bytes(const avs_conv_desc* d, int64_t rows_per_group) {
   const char* who = "avs_conv2d_bnstats_workspace_bytes";
   IgemmParams p{};
-  int st = conv_fill_params(d, (const void*)16, (const void*)16, nullptr, (void*)16, p, who);
+  int st = conv_geometry(d, false, p, who);
   if (st != AVS_OK) return st;
   if (p.M == 0) return 0;
+  IgemmPlan pl;
   int64_t ws = 0;
-  int tile_rows = 0;
-  st = bnstats_plan(d, rows_per_group, p, &ws, &tile_rows, who);
+  st = bnstats_plan(d, rows_per_group, false, p, pl, &ws, who);
   return st == AVS_OK ? ws : (int64_t)st;
 }
 
@@ -2237,20 +2232,17 @@ static int conv_bnstats(const avs_conv_desc* d, const void* d_x, const void* d_w
                         int64_t ws_bytes, const float* d_in_scale, const float* d_in_shift, int in_relu, avs_stream_t stream,
                         const char* who) {
   IgemmParams p{};
-  int st = conv_fill_params(d, d_x, d_w, nullptr, d_y, p, who);
+  int st = conv_geometry(d, false, p, who);
   if (st != AVS_OK) return st;
   if (p.M == 0) return AVS_OK;
+  conv_operands(p, d_x, d_w, nullptr, d_y);
+  const bool in_affine = d_in_scale || d_in_shift;
+  IgemmPlan pl;
   int64_t need = 0;
-  int tile_rows = 0;
-  st = bnstats_plan(d, rows_per_group, p, &need, &tile_rows, who);
+  st = bnstats_plan(d, rows_per_group, in_affine, p, pl, &need, who);
   if (st != AVS_OK) return st;
-  if (d_in_scale || d_in_shift) {
-    // the kernel igemm_dispatch_epi4 would pick: the nine-tap form on the pipelined 256-row tiles with the scalar tap walk
-    IgemmParams q = p;
-    q.lin_stride = -1;
-    AVS_REQUIRE(d->dtype == AVS_F16X2 && tile_rows == 256 && g_pipe3 && igemm_tap9_ok(q, 4) &&
-                    igemm_fastk_ok(q, 4, 16, q.N <= 64 ? 64 : 128),
-                AVS_E_UNSUPPORTED, "%s: the input affine rides in the AVS_F16X2 nine-tap form only (3x3 / stride 1 / pad 1 on "
+  if (in_affine) {
+    AVS_REQUIRE(pl.xin, AVS_E_UNSUPPORTED, "%s: the input affine rides in the AVS_F16X2 nine-tap form only (3x3 / stride 1 / pad 1 on "
                 "a dense input at most 63 pixels wide, 256-row tiles)", who);
     AVS_REQUIRE(d_in_scale && d_in_shift && avs_aligned16(d_in_scale) && avs_aligned16(d_in_shift), AVS_E_ARG,
                 "%s: in_scale / in_shift [groups, cin] must both be given, 16-byte aligned", who);
@@ -2264,15 +2256,14 @@ static int conv_bnstats(const avs_conv_desc* d, const void* d_x, const void* d_w
   AVS_REQUIRE(avs_aligned16(d_ws), AVS_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
   p.stat_part = reinterpret_cast<float*>(d_ws);
   p.rows_per_group = (int)rows_per_group;
-  st = igemm_launch(d->dtype, p, 1, (hipStream_t)stream, who);
+  st = igemm_run(pl, p, (hipStream_t)stream, who);
   if (st != AVS_OK) return st;
-  AVS_REQUIRE((p.tall ? 256 : 128) == tile_rows, AVS_E_ARG, "%s: tile choice changed between plan and launch", who);
   const long long groups = ((long long)p.M + rows_per_group - 1) / rows_per_group;
   const long long total = groups * p.N;
   long long gx = avs_cdiv(total, 256);
   if (gx > 8192) gx = 8192;
   hipLaunchKernelGGL(bn_fold_kernel, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, p.stat_part, total, p.N,
-                     p.stat_slots, tile_rows, (long long)rows_per_group, (long long)p.M, d_gamma, d_beta, eps, d_scale,
+                     p.stat_slots, pl.tile_rows, (long long)rows_per_group, (long long)p.M, d_gamma, d_beta, eps, d_scale,
                      d_shift, d->dtype == AVS_F16X2 ? 1 : 0);
   AVS_CHECK_LAUNCH(who);
   return AVS_OK;
@@ -2300,7 +2291,7 @@ extern "C" int avs_conv2d_nhwc_bnstats_xin(const avs_conv_desc* d, const void* d
 // ---- convolution + whole BatchNorm in one launch, statistics local to a tile (EPI_BNLOCAL) ----
 
 static int bnlocal_plan(const avs_conv_desc* d, int64_t rpg, IgemmParams& p, const char* who) {
-  int st = conv_fill_params(d, (const void*)16, (const void*)16, nullptr, (void*)16, p, who);
+  int st = conv_geometry(d, false, p, who);
   if (st != AVS_OK) return st;
   AVS_REQUIRE(rpg > 0, AVS_E_ARG, "%s: rows_per_group must be positive", who);
   if (p.M == 0) return AVS_OK;
@@ -2322,7 +2313,7 @@ static int bnlocal_plan(const avs_conv_desc* d, int64_t rpg, IgemmParams& p, con
 // ---- clustered tile-local BatchNorm (AVS_F16X2, the 224-row kernel): a group of `cluster` frames whose maps fill one
 // 224-row tile each (14 x 14: the reference's 4-frame micro-batches at ResNet-50's layer 3, features/extractors.py:48) ----
 static int bncluster_plan(const avs_conv_desc* d, int64_t rpg, int cluster, IgemmParams& p, const char* who) {
-  int st = conv_fill_params(d, (const void*)16, (const void*)16, nullptr, (void*)16, p, who);
+  int st = conv_geometry(d, false, p, who);
   if (st != AVS_OK) return st;
   AVS_REQUIRE(rpg > 0 && cluster >= 2 && cluster <= 16, AVS_E_ARG, "%s: rows_per_group > 0 and 2 <= cluster <= 16", who);
   if (p.M == 0) return AVS_OK;
@@ -2366,9 +2357,7 @@ extern "C" int avs_conv2d_nhwc_bncluster(const avs_conv_desc* d, const void* d_x
   const int64_t need = 64 + (int64_t)(p.M / p.tile_rows) * p.tiles_n * 4 * 64 * 8;
   AVS_REQUIRE(xchg_bytes >= need, AVS_E_WORKSPACE, "%s: exchange buffer %lld < %lld bytes", who, (long long)xchg_bytes,
               (long long)need);
-  p.x = (const char*)d_x;
-  p.w = (const char*)d_w;
-  p.y = (char*)d_y;
+  conv_operands(p, d_x, d_w, nullptr, d_y);
   p.gamma = d_gamma;
   p.beta = d_beta;
   p.eps = eps;
@@ -2402,9 +2391,7 @@ extern "C" int avs_conv2d_nhwc_bnlocal(const avs_conv_desc* d, const void* d_x, 
               "%s: residual rows must be 16-byte aligned and at least cout long", who);
   AVS_REQUIRE(!h2 || !d_residual || ((((uintptr_t)d_residual) & 31u) == 0 && ldr % 8 == 0), AVS_E_ALIGN,
               "%s: an AVS_F16X2 residual must be 32-byte aligned with a row stride in multiples of 8 slots", who);
-  p.x = (const char*)d_x;
-  p.w = (const char*)d_w;
-  p.y = (char*)d_y;
+  conv_operands(p, d_x, d_w, nullptr, d_y);
   p.rows_per_group = (int)rows_per_group;
   p.gamma = d_gamma;
   p.beta = d_beta;
@@ -2422,9 +2409,10 @@ extern "C" int avs_conv2d_nhwc_affine(const avs_conv_desc* d, const void* d_x, c
                                       const float* d_res_shift, avs_stream_t stream) {
   const char* who = "avs_conv2d_nhwc_affine";
   IgemmParams p{};
-  int st = conv_fill_params(d, d_x, d_w, nullptr, d_y, p, who);
+  int st = conv_geometry(d, false, p, who);
   if (st != AVS_OK) return st;
   if (p.M == 0) return AVS_OK;
+  conv_operands(p, d_x, d_w, nullptr, d_y);
   AVS_REQUIRE(d->dtype == AVS_F16X2, AVS_E_UNSUPPORTED, "%s: built for AVS_F16X2", who);
   AVS_REQUIRE(d->kh == 1 && d->kw == 1 && d->ph == 0 && d->pw == 0 && (long long)p.K * 4 > 128 && d->alpha == 1.0f,
               AVS_E_UNSUPPORTED, "%s: 1x1 convolutions without padding, more than 32 input channels, alpha = 1", who);

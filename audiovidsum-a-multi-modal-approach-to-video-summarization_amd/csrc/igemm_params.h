@@ -101,7 +101,47 @@ __device__ __forceinline__ uint4 avs_lds_read_b128(unsigned byte_addr) {
   return v;
 }
 
+// What igemm_plan() chooses for one call - which kernel (the template arguments of igemm_kernel, or the 224-row tile of
+// local224.hip) on which grid - from the dtype, the geometry and the options alone: it reads no operand.
+struct IgemmPlan {
+  int status;          // AVS_OK, or the status of the first of the plan's checks that failed
+  int operand_checks;  // how many of igemm_run's operand checks come before the point the plan reached (0..3)
+  int dtype, batch;
+  int es;              // bytes per element
+  int split;           // SPLIT: 0 operands as stored, 1 AVS_F32_SPLIT, 2 AVS_F16X2
+  int bn;              // columns of a tile: 64 / 96 / 128
+  bool acc64;
+  bool tall;           // the rules ask for the 256-row tiles
+  bool spatial;        // a tap can leave the image: the per-tap bounds tests are needed
+  long long lin_stride;  // IgemmParams::lin_stride
+  int rowb;            // bytes of a reduction step: 64 / 128
+  int epi;             // EPI_*
+  bool pipe;           // the 3-buffer hand-counted pipeline
+  int wr;              // rows of waves: 2 (128-row tiles) / 4 (256-row tiles)
+  bool fastk;          // the scalar tap walk
+  bool tap9, ap8, xin; // the shifted-row staging, the AVS_F16P8 input, the input affine
+  bool in_affine;      // the caller gives an input affine: only the XIN kernel may run
+  bool local224;       // the 224-row tile takes it
+  int tile_rows;       // rows of a tile that are used = the pitch between tiles
+  long long tiles_m;
+  int tiles_n;
+  long long grid;      // workgroups per batch entry = tiles_m * tiles_n; 0: nothing to launch
+};
+
+// The buffer window of the scalar tap walk (buffer_load ... lds): a tile's rows (at most 256, spread over whole images)
+// plus the tap walk, and bn rows of the weights, must each lie below 2 GiB; es = bytes per element
+inline bool igemm_buffer_window_ok(const IgemmParams& p, long long lin_stride, int es, int bn) {
+  const long long rows = 256;
+  long long extent;
+  if (lin_stride >= 0)
+    extent = rows * lin_stride + p.K;
+  else
+    extent = (rows / p.HoWo + 2) * p.x_img_stride + (long long)(p.K / (p.cin * p.KW) + p.ph) * p.x_row_stride +
+             (long long)(p.KW + p.pw) * p.x_px_stride + p.cin;
+  return extent * es < (1ll << 31) && (long long)bn * p.ldb * es + (long long)p.K * es < (1ll << 31) &&
+         p.x_img_stride >= 0 && p.x_row_stride >= 0 && p.x_px_stride >= 0;
+}
 
 // local224.hip: the AVS_F16X2 tile-local BatchNorm form on 224-row tiles (one group of 193..224 rows per tile)
-bool igemm_h2_local224_ok(const IgemmParams& p, int dtype);
+bool igemm_h2_local224_ok(const IgemmParams& p, int dtype, long long lin_stride);
 void igemm_h2_local224_launch(const IgemmParams& p, bool spatial, dim3 grid, hipStream_t stream);

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
 // The shapes the 224-row form takes: AVS_F16X2, one group of 193 .. 224 rows per tile, cout in multiples of 128, a
 // reduction walked by the scalar tap walk in 64-byte steps inside the 2 GiB buffer window, the caller not asking for
 // another tile (avs_conv_desc.variant: AVS_TILE_AUTO or AVS_TILE_224).
-bool igemm_h2_local224_ok(const IgemmParams& p, int dtype) {
+bool igemm_h2_local224_ok(const IgemmParams& p, int dtype, long long lin_stride) {
   const int tile_mode = p.variant & 3;
   if (dtype != AVS_F16X2 || !(tile_mode == AVS_TILE_AUTO || tile_mode == AVS_TILE_224)) return false;
   if (p.variant & AVS_STAGING_GENERIC) return false;
@@ -424,15 +424,7 @@ bool igemm_h2_local224_ok(const IgemmParams& p, int dtype) {
   if (p.tile_rows * cl != p.rows_per_group || p.tile_rows <= 192 || p.tile_rows > L_ROWS) return false;
   if (p.N % L_BN != 0 || p.M % p.rows_per_group != 0) return false;
   if (p.cin % L_STEP != 0 || p.K % L_STEP != 0 || p.K % p.cin != 0 || p.K / p.cin > 32) return false;
-  const long long rows = 256;
-  long long extent;
-  if (p.lin_stride >= 0)
-    extent = rows * p.lin_stride + p.K;
-  else
-    extent = (rows / p.HoWo + 2) * p.x_img_stride + (long long)(p.K / (p.cin * p.KW) + p.ph) * p.x_row_stride +
-             (long long)(p.KW + p.pw) * p.x_px_stride + p.cin;
-  return extent * 4 < (1ll << 31) && (long long)L_BN * p.ldb * 4 + (long long)p.K * 4 < (1ll << 31) &&
-         p.x_img_stride >= 0 && p.x_row_stride >= 0 && p.x_px_stride >= 0;
+  return igemm_buffer_window_ok(p, lin_stride, 4, L_BN);
 }
 
 void igemm_h2_local224_launch(const IgemmParams& p, bool spatial, dim3 grid, hipStream_t stream) {
