@@ -143,6 +143,11 @@ _SIGNATURES = {
     "avs_dtw_workspace_bytes": (c_int64, [c_int, c_int]),
     "avs_dtw_path_f64": (c_int, [P, c_int, c_int, P, c_int64, P, P, P, P]),
     "avs_gather_scale_f32": (c_int, [P, c_int64, c_int, P, P, c_int, P, P]),
+    "avs_cdist_batch_f64": (c_int, [P, c_int64, P, c_int64, c_int, P, c_int, P, c_int64, P, c_int64, P]),
+    "avs_dtw_batch_workspace_bytes": (c_int64, [c_int64]),
+    "avs_dtw_batch_f64": (c_int, [P, c_int64, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int64,
+                                  P, P, P, P, P]),
+    "avs_fused_gather_batch_f32": (c_int, [P, c_int64, c_int, P, c_int, P, c_int64, P, P, P, c_int64, P, P]),
 }
 
 _lib = None

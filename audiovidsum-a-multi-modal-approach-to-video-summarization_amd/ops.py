@@ -5,6 +5,7 @@ computation below is a call into libavsum_hip.so.
 import ctypes
 from ctypes import c_float, c_void_p
 
+import numpy as np
 import torch
 
 from . import _abi
@@ -15,7 +16,7 @@ __all__ = [
     "ACT_NONE", "ACT_RELU", "linear", "gemm_nt_batched", "conv2d", "conv2d_raw", "conv2d_split", "conv_bnlocal_tile_rows", "conv_bncluster_ok", "conv_bnstats_ok", "cluster_exchange_errors", "lstm_split_errors", "conv1x1_bn", "conv1x1_gram_bn", "bn_gram_affine", "gram_supported", "frames_normalize", "pull_copy", "stem_conv_bn_pool", "stem_h2_operands", "stem_conv_pool_h2", "resize_bilinear",
     "bn_batch_stats", "bn_apply", "bn_maxpool", "pool2d", "global_avgpool", "segment_mean", "hsv_frame_diff", "reflect_pad", "stft_f64", "stft_mel_fused", "power_mel",
     "clamp_topdb", "stft_mel_max", "stft_mel_segmean", "stft_mel_segmean_batch", "stft_mel_shots", "vggish_examples", "fill", "quantize", "resample", "lstm", "mha_batchaxis", "score_head", "mhsa_flash", "softmax_rows", "cdist", "dtw_path",
-    "gather_scale", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
+    "gather_scale", "FusionTables", "fusion_batch", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
 ]
 
 
@@ -1429,3 +1430,141 @@ def gather_scale(x, idx, w):
     check(lib().avs_gather_scale_f32(_p(x), x.stride(0), d, _p(idx), _p(w), count, _p(out), _stream()),
           "avs_gather_scale_f32")
     return out
+
+
+# --------------------------------------------------------------------------- batched fusion
+FUSION_MAX_N = 6400      # rows of the visual side of one pair (the per-pair limit of dtw_path)
+FUSION_SMALL_L = 64      # size classes by l = min(n, m): l <= 64 one wave per pair (four pairs per workgroup),
+FUSION_MID_L = 512       # l <= 512 one 256-thread workgroup per pair, above that one 1024-thread workgroup
+_FUSION_TILE = 32        # the cost kernel's output tile
+
+
+class FusionTables:
+    """The host plan of one batch layout for fusion_batch, built once from the host list of pairs
+    ``(v_row0, n, a_row0, m)``: pair p is rows v_row0 .. v_row0 + n of the visual matrix against rows a_row0 ..
+    a_row0 + m of the audio matrix.  Nothing is padded; the pairs may leave gaps and come in any order.
+
+    Host side (numpy): ``n``, ``m``, ``cell_off`` (first element of the pair's [n, m] block in the cost buffer and the
+    code workspace), ``path_off`` / ``path_cap`` (its path slot: n + m - 1 rows), ``row_off`` (first of its n row
+    counts), ``cls`` (size class 0/1/2), ``order`` (pairs sorted by class, longest sweep first inside a class),
+    ``class_count``, ``class_max_l``, ``tiles`` (pair, row tile, column tile), ``cells``, ``path_rows``, ``rows``,
+    ``workspace_bytes``.  Device side: ``pairs`` int64 [P, 8], ``order_t``, ``tiles_t``, ``row_pair`` int32 [rows].
+    ``device="cpu"`` keeps everything on the host (the table builder can be checked without a GPU)."""
+
+    def __init__(self, pairs, device=None):
+        arr = np.asarray(list(pairs), dtype=np.int64).reshape(-1, 4)
+        v0, n, a0, m = (arr[:, k].copy() for k in range(4))
+        if (n <= 0).any() or (m <= 0).any():
+            raise ValueError("fusion_batch: a pair is empty (n == 0 or m == 0)")
+        if (v0 < 0).any() or (a0 < 0).any():
+            raise ValueError("fusion_batch: negative row offset")
+        if (n > FUSION_MAX_N).any():
+            raise ValueError(f"fusion_batch: a pair has n = {int(n.max())} rows, above the LDS-resident limit {FUSION_MAX_N}")
+        if (m >= 1 << 30).any():
+            raise ValueError("fusion_batch: a pair has m >= 2^30 rows")
+        npairs = arr.shape[0]
+        self.npairs, self.v_row0, self.n, self.a_row0, self.m = npairs, v0, n, a0, m
+        self.v_rows_needed = int((v0 + n).max()) if npairs else 0
+        self.a_rows_needed = int((a0 + m).max()) if npairs else 0
+        ex = lambda x: np.concatenate([[0], np.cumsum(x)]).astype(np.int64)   # exclusive prefix sums (+ the total)
+        cell, path, row = ex(n * m), ex(n + m - 1), ex(n)
+        self.cell_off, self.path_off, self.row_off = cell[:-1], path[:-1], row[:-1]
+        self.path_cap = n + m - 1
+        self.cells, self.path_rows, self.rows = int(cell[-1]), int(path[-1]), int(row[-1])
+        small = np.minimum(n, m)
+        self.cls = (small > FUSION_SMALL_L).astype(np.int64) + (small > FUSION_MID_L)
+        # by class, then the most anti-diagonals first (neighbours in a class-0 workgroup sweep about as long); stable
+        self.order = np.lexsort((np.arange(npairs), -(n + m), self.cls)).astype(np.int32)
+        self.class_count = [int((self.cls == c).sum()) for c in range(3)]
+        self.class_max_l = [int(small[self.cls == c].max()) if self.class_count[c] else 0 for c in range(3)]
+        self.max_n = int(n.max()) if npairs else 0
+        ti, tj = -(-n // _FUSION_TILE), -(-m // _FUSION_TILE)
+        per = ti * tj
+        self.ntiles = int(per.sum())
+        tp = np.repeat(np.arange(npairs, dtype=np.int64), per)
+        k = np.arange(self.ntiles, dtype=np.int64) - np.repeat(ex(per)[:-1], per)
+        self.tiles = np.stack([tp, k // tj[tp], k % tj[tp]], 1).astype(np.int32).reshape(-1, 3)
+        self.row_pair_host = np.repeat(np.arange(npairs, dtype=np.int32), n)
+        self.workspace_bytes = (self.cells + 255) & ~255     # avs_dtw_batch_workspace_bytes: one code byte per cell
+        table = np.zeros((npairs, 8), dtype=np.int64)
+        for col, x in enumerate((v0, n, a0, m, self.cell_off, self.path_off, self.row_off)):
+            table[:, col] = x
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.pairs = torch.from_numpy(table).to(torch.device(device))
+        self.device = self.pairs.device
+        self.order_t = torch.from_numpy(self.order).to(self.device)
+        self.tiles_t = torch.from_numpy(self.tiles).to(self.device)
+        self.row_pair = torch.from_numpy(self.row_pair_host).to(self.device)
+        self._out = {}
+        self.out_offsets(None)
+
+    def out_rows(self, target_length=None):
+        """Rows each pair contributes to the fused output: min(n, target_length)."""
+        return self.n if target_length is None else np.minimum(self.n, max(int(target_length), 0))
+
+    def out_offsets(self, target_length=None):
+        """(device int64 [P + 1] row offsets of the fused output, host total) for a target length; uploaded once per
+        length and kept, so that a repeated fusion_batch call moves nothing between host and device."""
+        key = None if target_length is None else max(int(target_length), 0)
+        if key not in self._out:
+            off = np.concatenate([[0], np.cumsum(self.out_rows(key))]).astype(np.int64)
+            self._out[key] = (torch.from_numpy(off).to(self.device), int(off[-1]))
+        return self._out[key]
+
+
+def fusion_batch(tables, v, a, target_length=None, keep_cost=False):
+    """Cost matrix, exact DTW path and path-weighted gather (features/fusion.py:7-32) of every pair of ``tables`` in one
+    fixed set of launches: one for the cost tiles, one per non-empty size class for the DTW, one for the gather.  ``v``
+    [Rv, D] and ``a`` [Ra, D] are fp32 device matrices.  Returns a dict of device tensors:
+      fused [sum min(n, target_length), D] with out_offsets int64 [P + 1]; path int64 [sum (n + m - 1), 2] with
+      path_offsets int64 [P] (pair p's path is path[path_offsets[p] : path_offsets[p] + path_len[p]]); path_len int64 [P];
+      total float64 [P]; rowcount int32 [sum n] with row_offsets int64 [P]; cost float64 [sum n*m] (keep_cost only, pair
+      p's matrix row-major at tables.cell_off[p]).
+    Pair for pair the values are those of cdist / dtw_path / gather_scale.  Nothing synchronises with the host."""
+    if not isinstance(tables, FusionTables):
+        raise ValueError("fusion_batch: tables must be an ops.FusionTables")
+    for t, name in ((v, "v"), (a, "a")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"fusion_batch: {name} must be a device tensor (there is no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"fusion_batch: {name} must be float32, got {t.dtype}")
+        if t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"fusion_batch: {name} must be a contiguous 2-D matrix, got shape {tuple(t.shape)}")
+    if v.shape[1] != a.shape[1] or v.shape[1] == 0:
+        raise ValueError(f"fusion_batch: v and a must have the same number of columns, got {v.shape[1]} and {a.shape[1]}")
+    if tables.device != v.device or a.device != v.device:
+        raise ValueError("fusion_batch: tables, v and a must be on the same device")
+    if tables.v_rows_needed > v.shape[0] or tables.a_rows_needed > a.shape[0]:
+        raise ValueError(f"fusion_batch: the pairs reach row {tables.v_rows_needed} of v ({v.shape[0]} rows) and row "
+                         f"{tables.a_rows_needed} of a ({a.shape[0]} rows)")
+    if target_length is not None and int(target_length) < 0:
+        raise ValueError("fusion_batch: target_length must be >= 0")
+    dev, d, npairs = v.device, v.shape[1], tables.npairs
+    out_off, out_total = tables.out_offsets(target_length)
+    cost = torch.empty(max(tables.cells, 1), dtype=torch.float64, device=dev)
+    ws = torch.empty(max(tables.workspace_bytes, 256), dtype=torch.uint8, device=dev)
+    path = torch.empty((max(tables.path_rows, 1), 2), dtype=torch.int64, device=dev)
+    path_len = torch.empty(max(npairs, 1), dtype=torch.int64, device=dev)
+    total = torch.empty(max(npairs, 1), dtype=torch.float64, device=dev)
+    rowcount = torch.empty(max(tables.rows, 1), dtype=torch.int32, device=dev)
+    fused = torch.empty((out_total, d), dtype=torch.float32, device=dev)
+    if npairs:
+        check(lib().avs_cdist_batch_f64(_p(v), v.shape[0], _p(a), a.shape[0], d, _p(tables.pairs), npairs,
+                                        _p(tables.tiles_t), tables.ntiles, _p(cost), tables.cells, _stream()),
+              "avs_cdist_batch_f64")
+        cc, ml = tables.class_count, tables.class_max_l
+        check(lib().avs_dtw_batch_f64(_p(cost), tables.cells, _p(tables.pairs), npairs, _p(tables.order_t), cc[0], cc[1],
+                                      cc[2], ml[0], ml[1], ml[2], tables.max_n, _p(ws), ws.numel(), _p(path),
+                                      _p(path_len), _p(total), _p(rowcount), _stream()), "avs_dtw_batch_f64")
+        if out_total:
+            tl = FUSION_MAX_N if target_length is None else int(target_length)
+            check(lib().avs_fused_gather_batch_f32(_p(v), v.stride(0), d, _p(tables.pairs), npairs, _p(tables.row_pair),
+                                                   tables.rows, _p(out_off), _p(rowcount), _p(path_len), tl, _p(fused),
+                                                   _stream()), "avs_fused_gather_batch_f32")
+    res = {"fused": fused, "out_offsets": out_off, "path": path[:tables.path_rows], "path_offsets": tables.pairs[:, 5],
+           "path_len": path_len[:npairs], "total": total[:npairs], "rowcount": rowcount[:tables.rows],
+           "row_offsets": tables.pairs[:, 6]}
+    if keep_cost:
+        res["cost"] = cost[:tables.cells]
+    return res

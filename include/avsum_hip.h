@@ -709,6 +709,42 @@ int avs_gather_scale_f32(const float* d_x, int64_t ldx, int d, const int64_t* d_
                          const double* d_w, int count, float* d_out,
                          avs_stream_t stream);
 
+/* ---- batched fusion: P ragged (visual [n_p,D], audio [m_p,D]) pairs per call, a fixed number of launches ----------
+ * The pairs are row ranges of two row-major fp32 matrices; nothing is padded.  d_pairs is int64 [npairs, 8] =
+ * (v_row0, n, a_row0, m, cell_off, path_off, row_off, 0): cell_off = first element of the pair's row-major [n, m]
+ * block in the cost buffer (doubles) and in the code workspace (bytes), path_off = first row of its path slot
+ * (capacity n + m - 1 rows), row_off = first of its n row counts.  The tables are trusted: the caller (ops.FusionTables)
+ * guarantees that every range lies inside its buffer; the entry points check the host-side sizes only.  No entry
+ * point synchronises or reads a result back.                                                                        */
+
+/* Every pair's cost matrix, bit for bit avs_cdist_f64 of that pair.  d_tiles is int32 [ntiles, 3] = (pair, row tile,
+ * column tile) over 32x32 tiles; cells = the sum of n*m.                                                            */
+int avs_cdist_batch_f64(const float* d_v, int64_t v_rows, const float* d_a, int64_t a_rows, int d,
+                        const int64_t* d_pairs, int npairs, const int32_t* d_tiles, int64_t ntiles, double* d_cost,
+                        int64_t cells, avs_stream_t stream);
+
+/* Exact DTW of every pair (recurrence and tie order of avs_dtw_path_f64) + backtrack.  d_order is int32 [npairs]: the
+ * pairs sorted into three size classes by l = min(n, m): the first n_small have l <= 64 (one wave per pair, four
+ * pairs per workgroup), the next n_mid 64 < l <= 512 (256 threads per pair), the last n_large l > 512 (1024 threads);
+ * max_l_* is the largest l of each class (it sizes that launch's LDS) and max_n the largest n (<= 6400).  One launch
+ * per non-empty class.  Per pair: the path (int64 pairs, start to end) into its slot of d_path, d_path_len[p],
+ * d_total[p], and d_rowcount[row_off + i] = the number of path cells in row i.  The workspace holds one predecessor
+ * byte per cell.                                                                                                     */
+int64_t avs_dtw_batch_workspace_bytes(int64_t cells);
+int avs_dtw_batch_f64(const double* d_cost, int64_t cells, const int64_t* d_pairs, int npairs, const int32_t* d_order,
+                      int n_small, int n_mid, int n_large, int max_l_small, int max_l_mid, int max_l_large, int max_n,
+                      void* d_workspace, int64_t workspace_bytes, int64_t* d_path, int64_t* d_path_len,
+                      double* d_total, int32_t* d_rowcount, avs_stream_t stream);
+
+/* out[out_off[p] + i, :] = x[v_row0 + i, :] * float(double(rowcount[row_off + i]) / double(path_len[p])) for
+ * i < min(n_p, target_length): interpolate_features (features/fusion.py:21-32) of every pair, the unique path rows
+ * being 0..n-1.  d_row_pair is int32 [nrows] (nrows = the sum of n): the pair of each row count; d_out_off int64
+ * [npairs] the first output row of each pair.                                                                        */
+int avs_fused_gather_batch_f32(const float* d_x, int64_t ldx, int d, const int64_t* d_pairs, int npairs,
+                               const int32_t* d_row_pair, int64_t nrows, const int64_t* d_out_off,
+                               const int32_t* d_rowcount, const int64_t* d_path_len, int64_t target_length,
+                               float* d_out, avs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
