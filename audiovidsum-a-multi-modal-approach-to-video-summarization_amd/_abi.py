@@ -148,6 +148,9 @@ _SIGNATURES = {
     "avs_dtw_batch_f64": (c_int, [P, c_int64, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int64,
                                   P, P, P, P, P]),
     "avs_fused_gather_batch_f32": (c_int, [P, c_int64, c_int, P, c_int, P, c_int64, P, P, P, c_int64, P, P]),
+    "avs_segment_mean_mask": (c_int, [P, c_int, c_int64, P, c_int, P, P, P]),
+    "avs_rank_pair_counts": (c_int, [P, P, c_int, c_int64, P, c_int, P, c_int64, c_int, P, P]),
+    "avs_eval_fold": (c_int, [P, P, P, c_int64, P, c_int, c_int, P, P]),
 }
 
 _lib = None

@@ -16,7 +16,7 @@ __all__ = [
     "ACT_NONE", "ACT_RELU", "linear", "gemm_nt_batched", "conv2d", "conv2d_raw", "conv2d_split", "conv_bnlocal_tile_rows", "conv_bncluster_ok", "conv_bnstats_ok", "cluster_exchange_errors", "lstm_split_errors", "conv1x1_bn", "conv1x1_gram_bn", "bn_gram_affine", "gram_supported", "frames_normalize", "pull_copy", "stem_conv_bn_pool", "stem_h2_operands", "stem_conv_pool_h2", "resize_bilinear",
     "bn_batch_stats", "bn_apply", "bn_maxpool", "pool2d", "global_avgpool", "segment_mean", "hsv_frame_diff", "reflect_pad", "stft_f64", "stft_mel_fused", "power_mel",
     "clamp_topdb", "stft_mel_max", "stft_mel_segmean", "stft_mel_segmean_batch", "stft_mel_shots", "vggish_examples", "fill", "quantize", "resample", "lstm", "mha_batchaxis", "score_head", "mhsa_flash", "softmax_rows", "cdist", "dtw_path",
-    "gather_scale", "FusionTables", "fusion_batch", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
+    "gather_scale", "FusionTables", "fusion_batch", "EvalTables", "eval_counts", "segment_mean_mask", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
 ]
 
 
@@ -1568,3 +1568,124 @@ def fusion_batch(tables, v, a, target_length=None, keep_cost=False):
     if keep_cost:
         res["cost"] = cost[:tables.cells]
     return res
+
+
+# --------------------------------------------------------------------------- batched evaluation
+EVAL_MAX_T = 32768       # rows of one video: 4 T^4 < 2^63, so the fold's sums and the host's products fit int64
+EVAL_TILE = 256          # rows of a video per workgroup of the pair-count kernel
+EVAL_CHUNK = 1024        # columns it stages through LDS per step
+EVAL_COLUMNS = ("T", "n_pred", "n_tgt", "tp", "S2", "E_x", "E_y", "S_xy", "S_xx", "S_yy")
+_EVAL_DTYPES = {torch.float32: 4, torch.float64: 8}
+
+
+class EvalTables:
+    """The host plan of one batch layout for eval_counts, built once from the host row offsets [V + 1] of the videos
+    in the concatenated score vectors (video v is rows offsets[v] .. offsets[v + 1]).
+
+    Host side (numpy): ``offsets``, ``lengths``, ``nvideos``, ``rows`` (= offsets[-1], the rows the vectors must have),
+    ``max_t``, ``tiles`` int32 [ntiles, 2] = (video, row tile of 256 rows), ``ntiles``.  Device side: ``offsets_t``
+    int64 [V + 1], ``tiles_t``.  ``device="cpu"`` keeps everything on the host (the builder can be checked without a
+    GPU).  Refused, each with a ValueError: a video shorter than 2 rows (no pair to rank) or longer than 32768,
+    decreasing or negative offsets, 2^31 rows or more."""
+
+    def __init__(self, offsets_host, device=None):
+        off = np.asarray(offsets_host, dtype=np.int64).reshape(-1)
+        if off.size == 0:
+            raise ValueError("eval_counts: offsets must hold V + 1 entries (a single 0 for an empty batch)")
+        if off[0] < 0:
+            raise ValueError("eval_counts: negative row offset")
+        t = np.diff(off)
+        if (t < 0).any():
+            raise ValueError("eval_counts: the offsets decrease")
+        if off[-1] >= 1 << 31:
+            raise ValueError(f"eval_counts: {int(off[-1])} rows, the kernels index rows below 2^31")
+        if (t < 2).any():
+            raise ValueError(f"eval_counts: a video has {int(t.min())} rows; a rank correlation needs at least 2")
+        if (t > EVAL_MAX_T).any():
+            raise ValueError(f"eval_counts: a video has {int(t.max())} rows, above the int64-exact limit {EVAL_MAX_T}")
+        self.offsets, self.lengths, self.nvideos = off, t, int(t.size)
+        self.rows = int(off[-1])
+        self.max_t = int(t.max()) if t.size else 0
+        per = -(-t // EVAL_TILE)
+        self.ntiles = int(per.sum())
+        vid = np.repeat(np.arange(self.nvideos, dtype=np.int64), per)
+        first = np.concatenate([[0], np.cumsum(per)])[:-1].astype(np.int64)
+        k = np.arange(self.ntiles, dtype=np.int64) - np.repeat(first, per)
+        self.tiles = np.stack([vid, k], 1).astype(np.int32).reshape(-1, 2)
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.offsets_t = torch.from_numpy(off).to(torch.device(device))
+        self.device = self.offsets_t.device
+        self.tiles_t = torch.from_numpy(self.tiles).to(self.device)
+
+
+def _eval_vector(t, name, what, dtypes):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{what}: {name} must be a device tensor (there is no CPU fallback)")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{what}: {name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous vector, got shape {tuple(t.shape)}")
+
+
+def _segment_mean_mask(x, offsets_t, nseg, mask):
+    mean = torch.empty(nseg, dtype=x.dtype, device=x.device)
+    check(lib().avs_segment_mean_mask(_p(x), _EVAL_DTYPES[x.dtype], x.shape[0], _p(offsets_t), nseg, _p(mean), _p(mask),
+                                      _stream()), "avs_segment_mean_mask")
+    return mean
+
+
+def segment_mean_mask(x, offsets):
+    """(mean [V] in x's dtype, mask uint8 [R]) of the segments offsets[v] .. offsets[v + 1] of the float32 / float64
+    device vector ``x``: mean[v] is np.mean(x[a:b]) bit for bit (numpy's reduction order) and mask[r] = x[r] > mean[v]
+    - evaluation.metrics.select_frames per segment without a download.  ``offsets``: host sequence or int64 device
+    tensor [V + 1], non-decreasing, inside x; rows outside every segment get mask 0; an empty segment's mean is NaN."""
+    _eval_vector(x, "x", "segment_mean_mask", (torch.float32, torch.float64))
+    if isinstance(offsets, torch.Tensor):
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1 or not offsets.is_contiguous():
+            raise ValueError("segment_mean_mask: offsets must be a contiguous int64 vector of V + 1 entries")
+        if offsets.device != x.device:
+            raise ValueError("segment_mean_mask: x and offsets must be on the same device")
+        off_t = offsets
+    else:
+        off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        if off.size < 1 or off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > x.shape[0]:
+            raise ValueError(f"segment_mean_mask: offsets must be non-decreasing and lie in 0 .. {x.shape[0]}")
+        off_t = torch.from_numpy(off).to(x.device)
+    mask = torch.zeros(x.shape[0], dtype=torch.uint8, device=x.device)
+    return _segment_mean_mask(x, off_t, off_t.numel() - 1, mask), mask
+
+
+def eval_counts(tables, pred, target):
+    """The integers the per-video metrics of scripts/evaluate.py:21-42 reduce to, for every video of ``tables`` in four
+    launches: int64 [V, 10] device tensor, columns EVAL_COLUMNS = (T, n_pred, n_tgt, tp, S2, E_x, E_y, S_xy, S_xx,
+    S_yy).  ``pred`` float32 [R] and ``target`` float32 or float64 [R] are device vectors (values finite); the masks
+    are x > np.mean(x) per video with numpy's reduction order in each vector's own dtype.  Nothing synchronises with
+    the host; evaluation.metrics.metrics_from_counts finishes the O(V) float work after one download."""
+    if not isinstance(tables, EvalTables):
+        raise ValueError("eval_counts: tables must be an ops.EvalTables")
+    _eval_vector(pred, "pred", "eval_counts", (torch.float32,))
+    _eval_vector(target, "target", "eval_counts", (torch.float32, torch.float64))
+    if tables.device != pred.device or target.device != pred.device:
+        raise ValueError("eval_counts: tables, pred and target must be on the same device")
+    rows = pred.shape[0]
+    if target.shape[0] != rows or tables.rows > rows:
+        raise ValueError(f"eval_counts: the videos reach row {tables.rows}; pred has {rows} rows and target "
+                         f"{target.shape[0]}")
+    if rows >= 1 << 31:
+        raise ValueError(f"eval_counts: {rows} rows, the kernels index rows below 2^31")
+    dev, nv = pred.device, tables.nvideos
+    out = torch.empty((nv, len(EVAL_COLUMNS)), dtype=torch.int64, device=dev)
+    if nv == 0:
+        return out
+    mask_x = torch.empty(rows, dtype=torch.uint8, device=dev)
+    mask_y = torch.empty(rows, dtype=torch.uint8, device=dev)
+    counts = torch.empty((5, rows), dtype=torch.int32, device=dev)
+    _segment_mean_mask(pred, tables.offsets_t, nv, mask_x)
+    _segment_mean_mask(target, tables.offsets_t, nv, mask_y)
+    check(lib().avs_rank_pair_counts(_p(pred), _p(target), _EVAL_DTYPES[target.dtype], rows, _p(tables.offsets_t), nv,
+                                     _p(tables.tiles_t), tables.ntiles, tables.max_t, _p(counts), _stream()),
+          "avs_rank_pair_counts")
+    check(lib().avs_eval_fold(_p(counts), _p(mask_x), _p(mask_y), rows, _p(tables.offsets_t), nv, tables.max_t, _p(out),
+                              _stream()), "avs_eval_fold")
+    return out

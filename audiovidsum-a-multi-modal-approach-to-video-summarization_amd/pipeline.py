@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .evaluation.metrics import select_frames
+from .evaluation.metrics import select_frames, select_mask_device
 
 
 class _HostStager:
@@ -311,3 +311,9 @@ class FrameScoringPipeline:
         """Selection rule of scripts/evaluate.py:26 per video, on the host (bit-exact numpy)."""
         host = scores.detach().cpu().numpy()
         return [select_frames(host[a:b]) for a, b in zip(video_offsets[:-1], video_offsets[1:])]
+
+    @staticmethod
+    def select_device(scores, video_offsets):
+        """The same selection as a uint8 device mask [N] (1 = selected), without downloading the scores: the per-video
+        mean is summed on the device in numpy's order, so mask[a:b] is exactly select()'s indices of that video."""
+        return select_mask_device(scores, video_offsets)

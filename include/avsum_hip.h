@@ -745,6 +745,34 @@ int avs_fused_gather_batch_f32(const float* d_x, int64_t ldx, int d, const int64
                                const int32_t* d_rowcount, const int64_t* d_path_len, int64_t target_length,
                                float* d_out, avs_stream_t stream);
 
+/* ---- batched evaluation: the mean-threshold F1 and both rank correlations of V videos per call ---------------------
+ * (scripts/evaluate.py:21-42, evaluation/metrics.py:1-9.)  The videos are the segments [offsets[v], offsets[v + 1]) of
+ * concatenated vectors; d_offsets is int64 [nseg + 1], non-decreasing and inside the vectors (trusted, as the pair
+ * tables above: ops.EvalTables guarantees it).  Every result is an integer or is computed in one fixed order, so two
+ * calls on the same input give the same bytes.  No entry point synchronises or reads a result back.                  */
+
+/* mean[v] = np.mean(x[a:b]) bit for bit - numpy's own order: buffers of 8192 elements summed left to right, each
+ * buffer by numpy's pairwise rule (eight strided accumulators below 128 elements, halves cut at a multiple of 8
+ * above), sum / n in the element type - and mask[r] = x[r] > mean[v] for the rows of segment v (rows outside every
+ * segment are not written).  elem_bytes: 4 = float32, 8 = float64 (d_x and d_mean of that type).  One workgroup per
+ * segment.                                                                                                           */
+int avs_segment_mean_mask(const void* d_x, int elem_bytes, int64_t rows, const int64_t* d_offsets, int nseg,
+                          void* d_mean, uint8_t* d_mask, avs_stream_t stream);
+
+/* Per row i of every video, over all j of the same video: d_counts int32 [5, rows] = planes (#{x_j < x_i},
+ * #{x_j == x_i} self included, the same two on y, sum_j sign(x_i - x_j) sign(y_i - y_j)), x = d_pred (float32),
+ * y = d_target (target_bytes 4 = float32, 8 = float64).  IEEE comparisons (-0.0 == 0.0); the inputs must be finite.
+ * d_tiles is int32 [ntiles, 2] = (video, row tile) over tiles of 256 rows; max_t = the longest video (<= 32768).      */
+int avs_rank_pair_counts(const float* d_pred, const void* d_target, int target_bytes, int64_t rows,
+                         const int64_t* d_offsets, int nseg, const int32_t* d_tiles, int64_t ntiles, int max_t,
+                         int32_t* d_counts, avs_stream_t stream);
+
+/* d_out int64 [nseg, 10] = (T, n_pred, n_tgt, tp, S2, E_x, E_y, S_xy, S_xx, S_yy) per video: the mask sums and their
+ * overlap, S2 = sum s = 2 (concordant - discordant), E = sum eq (tied pairs = (E - T) / 2), and the sums of products
+ * of the doubled average ranks 2r = 2 less + eq + 1.  With T <= 32768 every sum, and T * S_xy on the host, fits int64. */
+int avs_eval_fold(const int32_t* d_counts, const uint8_t* d_mask_pred, const uint8_t* d_mask_target, int64_t rows,
+                  const int64_t* d_offsets, int nseg, int max_t, int64_t* d_out, avs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
