@@ -151,6 +151,9 @@ _SIGNATURES = {
     "avs_segment_mean_mask": (c_int, [P, c_int, c_int64, P, c_int, P, P, P]),
     "avs_rank_pair_counts": (c_int, [P, P, c_int, c_int64, P, c_int, P, c_int64, c_int, P, P]),
     "avs_eval_fold": (c_int, [P, P, P, c_int64, P, c_int, c_int, P, P]),
+    "avs_seq_shift_rows_f32": (c_int, [P, c_int64, c_int, c_int, c_int64, P, c_int, c_int, P, c_int64, P]),
+    "avs_seq_mse_f32": (c_int, [P, P, c_int, c_int64, P, c_int, P, P]),
+    "avs_seq_mse_bwd_f32": (c_int, [P, P, P, c_int, c_int64, P, c_int, c_int, P, P]),
 }
 
 _lib = None

@@ -1,9 +1,11 @@
 """Training-mode forward + backward of AVBiLSTMModel on the MI355X (scripts/train_av_model.py:86-96).
 
 A torch.autograd.Function whose forward and backward are sequences of libavsum_hip.so calls: torch only owns
-the tensors, the RNG that draws the Dropout masks, and (in the caller's script) the loss and AdamW.  One
-sequence per call (the reference trains with B = 1, train_av_model.py:64,86-88); with B = 1 the attention is
-out_proj(v_proj(x)) and the query/key projections receive exactly zero gradient.
+the tensors, the RNG that draws the Dropout masks, and (in the caller's script) AdamW.  The rows are those of V >= 1
+videos, concatenated, with the device table of their row offsets: every video is its own B = 1 call of the reference
+model (the reference trains with B = 1, train_av_model.py:64,86-88) - its own four recurrences, and with B = 1 the
+attention is out_proj(v_proj(x)) and the query/key projections receive exactly zero gradient.  Everything
+else is row-wise.  AVBiLSTMModel.forward (V = 1, seq = [0, T]) and AVBiLSTMModel.train_rows both come through here.
 """
 import torch
 
@@ -14,12 +16,13 @@ DROPOUT_P = 0.3  # models/av_model.py:11,14
 
 class ScorerTrainFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, visual, audio, keep_v, keep_a, *params):
+    def forward(ctx, model, visual, audio, keep_v, keep_a, seq, *params):
+        """visual [R, Dv], audio [R, Da], keep_* [R, hidden]; seq int64 [V + 1] on the device: the row offsets of the
+        videos (starts at 0, increases, ends at R - the caller has validated it on the host)."""
         names = [n for n, _ in model.named_parameters()]
         pm = dict(zip(names, params))
         dev = visual.device
         t = visual.shape[0]
-        seq = torch.tensor([0, t], dtype=torch.int64, device=dev)
         hidden = pm["visual_fc.0.weight"].shape[0]
         e = 2 * hidden
 
@@ -77,31 +80,31 @@ class ScorerTrainFunction(torch.autograd.Function):
         g["attention.out_proj.weight"] = ops.grad_weight(dattn, val)
         g["attention.out_proj.bias"] = ops.colsum(dattn)
         dval = ops.grad_input(dattn, w_o)
-        gw_in = torch.zeros_like(pm["attention.in_proj_weight"])
-        gb_in = torch.zeros_like(pm["attention.in_proj_bias"])
-        gw_in[2 * e:3 * e] = ops.grad_weight(dval, fused)
-        gb_in[2 * e:3 * e] = ops.colsum(dval)
+        gw_in = torch.empty_like(pm["attention.in_proj_weight"])
+        gb_in = torch.empty_like(pm["attention.in_proj_bias"])
+        ops.fill(gw_in[:2 * e], 0.0)                                   # query / key rows: exactly zero
+        ops.fill(gb_in[:2 * e], 0.0)
+        ops.grad_weight(dval, fused, out=gw_in[2 * e:3 * e])
+        ops.colsum(dval, out=gb_in[2 * e:3 * e])
         g["attention.in_proj_weight"], g["attention.in_proj_bias"] = gw_in, gb_in
         dfused = ops.grad_input(dval, w_v)
         dinputs = {}
         whh, gates, cell, hid = ctx.lstm
-        t = fused.shape[0]
         da_all = ops.lstm_bwd(dfused, 0, gates, cell, whh, hid, 4, 0b1010, ctx.seq)   # [T, 4 * 4H], one launch
         for tag, fc, lstm in (("v", "visual_fc.0.", "visual_bilstm."), ("a", "audio_fc.0.", "audio_bilstm.")):
             x, r, keep, emb, wih, col = ctx.saved[tag]
             da = da_all[:, col * 4:(col + 2 * hid) * 4]                                  # this BiLSTM's [T, 2*4H]
             gwih = ops.grad_weight(da, emb)                                             # [8H, hidden]
             gb = ops.colsum(da)
-            # h_{t-1} of each direction: forward = the previous row, reverse = the next row (zero at the start)
-            hprev = torch.zeros((t, 2 * hid), dtype=torch.float32, device=x.device)
-            if t > 1:
-                hprev[1:, :hid] = fused[:-1, col:col + hid]
-                hprev[:-1, hid:] = fused[1:, col + hid:col + 2 * hid]
+            # h_{t-1} of each direction: forward = the previous row, reverse = the next row, zero at the first step of
+            # every video (never the last state of the video before it)
+            hprev_f = ops.seq_shift_rows(fused, col, hid, ctx.seq, 1)
+            hprev_r = ops.seq_shift_rows(fused, col + hid, hid, ctx.seq, -1)
             g[lstm + "weight_ih_l0"], g[lstm + "weight_ih_l0_reverse"] = gwih[:4 * hid], gwih[4 * hid:]
             g[lstm + "bias_ih_l0"] = g[lstm + "bias_hh_l0"] = gb[:4 * hid]
             g[lstm + "bias_ih_l0_reverse"] = g[lstm + "bias_hh_l0_reverse"] = gb[4 * hid:]
-            g[lstm + "weight_hh_l0"] = ops.grad_weight(da[:, :4 * hid], hprev[:, :hid])
-            g[lstm + "weight_hh_l0_reverse"] = ops.grad_weight(da[:, 4 * hid:], hprev[:, hid:])
+            g[lstm + "weight_hh_l0"] = ops.grad_weight(da[:, :4 * hid], hprev_f)
+            g[lstm + "weight_hh_l0_reverse"] = ops.grad_weight(da[:, 4 * hid:], hprev_r)
             demb = ops.grad_input(da, wih)
             dr = ops.relu_dropout_bwd(demb, r, keep)
             g[fc + "weight"] = ops.grad_weight(dr, x)
@@ -109,7 +112,7 @@ class ScorerTrainFunction(torch.autograd.Function):
             dinputs[tag] = dr
         dvis = ops.grad_input(dinputs["v"], pm["visual_fc.0.weight"]) if ctx.need_inputs[0] else None
         daud = ops.grad_input(dinputs["a"], pm["audio_fc.0.weight"]) if ctx.need_inputs[1] else None
-        return (None, dvis, daud, None, None) + tuple(g[n].reshape(pm[n].shape) for n in ctx.names)
+        return (None, dvis, daud, None, None, None) + tuple(g[n].reshape(pm[n].shape) for n in ctx.names)
 
 
 def dropout_keep(shape, device, p=DROPOUT_P):

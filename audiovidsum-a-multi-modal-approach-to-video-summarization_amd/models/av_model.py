@@ -108,6 +108,48 @@ class AVBiLSTMModel(nn.Module):
         hid64 = ops.linear(attn_out, s0.weight, s0.bias, ops.ACT_RELU)
         return ops.score_head(hid64, s2.weight.reshape(-1), s2.bias)
 
+    # ------------------------------------------------------------------ training on a ragged batch of videos
+    def train_rows(self, visual_rows, audio_rows, offsets):
+        """Scores, with autograd attached, for the rows of V videos in one pass: the training-mode counterpart of
+        score_rows and the V-video form of what forward() does for B = 1.
+
+        visual_rows [R, visual_dim], audio_rows [R, audio_dim] (fp32, device): the videos' rows concatenated;
+        ``offsets``: HOST int64 array-like [V + 1] of their row offsets (or an ops.SeqTable built from it, to share one
+        upload with ops.seq_mse).  It is validated on the host - starts at 0, strictly increasing (an empty video is
+        refused), ends at R, each with a ValueError - and uploaded once.  Returns fp32 [R].
+
+        Every video is its own B = 1 call of the reference model: its own four recurrences, attention over a single
+        key.  Video v's scores are bit for bit what ``model(visual_v[None], audio_v[None])`` returns for the same
+        Dropout mask rows.  Train mode: Dropout active - ONE dropout_keep((R, hidden)) draw for the visual branch, then
+        one for the audio branch, so for V > 1 torch's RNG is consumed differently from V per-video calls (which draw
+        visual, audio, visual, audio, ...): the same distribution, other masks.  Tests inject
+        ``model._dropout_keep = (keep_v, keep_a)``, [R, hidden] each.  Eval mode with gradients enabled: keep masks of
+        ones, as forward() does."""
+        if not visual_rows.is_cuda or not audio_rows.is_cuda:
+            raise RuntimeError("AVBiLSTMModel runs on the MI355X HIP path only: move inputs with .cuda()")
+        if visual_rows.dim() != 2 or audio_rows.dim() != 2 or visual_rows.shape[0] != audio_rows.shape[0]:
+            raise ValueError(f"expected visual_rows [R,Dv] and audio_rows [R,Da], got {tuple(visual_rows.shape)} / "
+                             f"{tuple(audio_rows.shape)}")
+        rows = visual_rows.shape[0]
+        table = offsets if isinstance(offsets, ops.SeqTable) else ops.SeqTable(offsets, rows, visual_rows.device)
+        if table.rows != rows or table.device != visual_rows.device:
+            raise ValueError(f"the offsets end at {table.rows} on {table.device}; the batch has {rows} rows on "
+                             f"{visual_rows.device}")
+        from ._scorer_train import ScorerTrainFunction, dropout_keep
+        v = visual_rows.float().contiguous()
+        a = audio_rows.float().contiguous()
+        hidden = self.visual_fc[0].out_features
+        if self.training:
+            masks = getattr(self, "_dropout_keep", None)  # tests inject fixed masks here
+            keep_v, keep_a = masks if masks is not None else (dropout_keep((rows, hidden), v.device),
+                                                              dropout_keep((rows, hidden), v.device))
+            if tuple(keep_v.shape) != (rows, hidden) or tuple(keep_a.shape) != (rows, hidden):
+                raise ValueError(f"the Dropout masks must be [{rows}, {hidden}]")
+        else:
+            keep_v = keep_a = torch.ones((rows, hidden), dtype=torch.float32, device=v.device)
+        return ScorerTrainFunction.apply(self, v, a, keep_v, keep_a, table.offsets_t,
+                                         *[p for _, p in self.named_parameters()])
+
     def forward(self, visual, audio):
         if not visual.is_cuda or not audio.is_cuda:
             raise RuntimeError("AVBiLSTMModel runs on the MI355X HIP path only: move inputs with .cuda()")
@@ -134,7 +176,9 @@ class AVBiLSTMModel(nn.Module):
                                                                   dropout_keep((t, hidden), v.device))
             else:
                 keep_v = keep_a = torch.ones((t, hidden), dtype=torch.float32, device=v.device)
-            scores = ScorerTrainFunction.apply(self, v, a, keep_v, keep_a, *[p for _, p in self.named_parameters()])
+            seq = torch.tensor([0, t], dtype=torch.int64, device=v.device)
+            scores = ScorerTrainFunction.apply(self, v, a, keep_v, keep_a, seq,
+                                               *[p for _, p in self.named_parameters()])
             return scores.view(b, t, 1).squeeze()
         if needs_grad:
             # eval mode, B > 1, autograd on: the inference path below builds no graph - refuse instead of returning

@@ -17,6 +17,7 @@ __all__ = [
     "bn_batch_stats", "bn_apply", "bn_maxpool", "pool2d", "global_avgpool", "segment_mean", "hsv_frame_diff", "reflect_pad", "stft_f64", "stft_mel_fused", "power_mel",
     "clamp_topdb", "stft_mel_max", "stft_mel_segmean", "stft_mel_segmean_batch", "stft_mel_shots", "vggish_examples", "fill", "quantize", "resample", "lstm", "mha_batchaxis", "score_head", "mhsa_flash", "softmax_rows", "cdist", "dtw_path",
     "gather_scale", "FusionTables", "fusion_batch", "EvalTables", "eval_counts", "segment_mean_mask", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
+    "SeqTable", "seq_shift_rows", "seq_mse",
 ]
 
 
@@ -1297,17 +1298,22 @@ def transpose_padded(x2d, pad=4):
     _rowmajor2d(x2d, "x")
     rows, cols = x2d.shape
     rp = (rows + pad - 1) // pad * pad
-    out = torch.zeros((cols, rp), dtype=torch.float32, device=x2d.device)
+    out = torch.empty((cols, rp), dtype=torch.float32, device=x2d.device)
+    if rp != rows:      # the transpose writes columns 0 .. rows - 1 of every row: only a padded tail needs the zeros
+        fill(out, 0.0)
     check(lib().avs_transpose_f32(_p(x2d), rows, cols, x2d.stride(0) if rows > 1 else cols, _p(out), rp, _stream()),
           "avs_transpose_f32")
     return out
 
 
-def colsum(x2d, row_weight=None):
+def colsum(x2d, row_weight=None, out=None):
     _f32(x2d, "x")
     _rowmajor2d(x2d, "x")
     rows, cols = x2d.shape
-    out = torch.empty(cols, dtype=torch.float32, device=x2d.device)
+    if out is None:
+        out = torch.empty(cols, dtype=torch.float32, device=x2d.device)
+    elif out.dtype != torch.float32 or out.shape != (cols,) or not out.is_contiguous():
+        raise ValueError("colsum: out must be a contiguous float32 vector with one entry per column")
     check(lib().avs_colsum_f32(_p(x2d), rows, cols, x2d.stride(0) if rows > 1 else cols, _p(row_weight), _p(out),
                                _stream()), "avs_colsum_f32")
     return out
@@ -1371,13 +1377,17 @@ def lstm_bwd(dout, out_col0, gates, cell, whh, hidden, ndir, reverse_mask, seq_r
     return dxproj
 
 
-def grad_weight(dy, x):
-    """dW [N, K] = dy[T, N]^T . x[T, K]  (NT GEMM on transposed, zero-padded copies)."""
+def grad_weight(dy, x, out=None):
+    """dW [N, K] = dy[T, N]^T . x[T, K]  (NT GEMM on transposed, zero-padded copies).  ``out``: a contiguous [N, K] view
+    to write into (e.g. the value rows of the attention's in_proj gradient)."""
     dyt = transpose_padded(dy)
     xt = transpose_padded(x)
     n, tp = dyt.shape
     k = xt.shape[0]
-    out = torch.empty((n, k), dtype=torch.float32, device=dy.device)
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float32, device=dy.device)
+    elif out.dtype != torch.float32 or out.shape != (n, k) or not out.is_contiguous():
+        raise ValueError(f"grad_weight: out must be a contiguous float32 [{n}, {k}]")
     gemm_nt_batched(AVS_F32, n, k, tp, dyt, 0, tp, 0, xt, 0, tp, 0, out, 0, k, 0)
     return out
 
@@ -1689,3 +1699,115 @@ def eval_counts(tables, pred, target):
     check(lib().avs_eval_fold(_p(counts), _p(mask_x), _p(mask_y), rows, _p(tables.offsets_t), nv, tables.max_t, _p(out),
                               _stream()), "avs_eval_fold")
     return out
+
+
+# --------------------------------------------------------------------------- batched training
+class SeqTable:
+    """Row offsets of a ragged batch of V videos (video v is rows offsets[v] .. offsets[v + 1] of the concatenated
+    rows), validated on the host and uploaded ONCE: ``offsets`` / ``lengths`` (numpy int64), ``nseq``, ``rows``,
+    ``max_t`` and the device copy ``offsets_t`` int64 [V + 1] that the recurrences, seq_shift_rows and seq_mse read.
+    ``rows``: the row count the offsets must end at (None: wherever they end).  Refused with a ValueError: fewer than
+    one video, offsets that do not start at 0, an empty video (offsets must increase strictly), a last offset other than
+    ``rows``, 2^31 rows or more.  ``device="cpu"`` keeps the table on the host (the builder is checked without a GPU)."""
+
+    def __init__(self, offsets_host, rows=None, device=None):
+        if isinstance(offsets_host, torch.Tensor):
+            if offsets_host.is_cuda:
+                raise ValueError("SeqTable: the offsets are a HOST array (they are validated before the upload)")
+            offsets_host = offsets_host.numpy()
+        off = np.array(offsets_host, dtype=np.int64).reshape(-1)
+        if off.size < 2:
+            raise ValueError("SeqTable: offsets must hold V + 1 entries for V >= 1 videos")
+        if off[0] != 0:
+            raise ValueError(f"SeqTable: offsets must start at 0, got {int(off[0])}")
+        t = np.diff(off)
+        if (t <= 0).any():
+            raise ValueError("SeqTable: an empty video (the offsets must increase strictly)")
+        if rows is not None and off[-1] != rows:
+            raise ValueError(f"SeqTable: the offsets end at {int(off[-1])}, the batch has {int(rows)} rows")
+        if off[-1] >= 1 << 31:
+            raise ValueError(f"SeqTable: {int(off[-1])} rows, the kernels index rows below 2^31")
+        self.offsets, self.lengths, self.nseq = off, t, int(t.size)
+        self.rows, self.max_t = int(off[-1]), int(t.max())
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.offsets_t = torch.from_numpy(off).to(torch.device(device))
+        self.device = self.offsets_t.device
+
+
+def _seq_table(offsets, rows, device, what):
+    if isinstance(offsets, SeqTable):
+        if offsets.rows != rows:
+            raise ValueError(f"{what}: the offsets end at {offsets.rows}, the batch has {rows} rows")
+        if offsets.device != device:
+            raise ValueError(f"{what}: the offsets table is on {offsets.device}, the rows on {device}")
+        return offsets
+    return SeqTable(offsets, rows, device)
+
+
+def seq_shift_rows(src, col0, cols, offsets_t, direction, out=None):
+    """out[r] = src[r - direction, col0:col0 + cols] where that row belongs to the same sequence as r, else 0: h_{t-1}
+    of a recurrence from its outputs (direction +1: forward, the previous row; -1: reverse, the next row).  Exact
+    copies.  ``src`` fp32 [R, C] device, unit column stride; ``offsets_t`` int64 [V + 1] device (SeqTable.offsets_t:
+    starts at 0, increases, ends at R).  Returns fp32 [R, cols]."""
+    _dev(src, offsets_t)
+    _f32(src, "src")
+    _rowmajor2d(src, "src")
+    rows, width = src.shape
+    if direction not in (1, -1):
+        raise ValueError(f"seq_shift_rows: direction must be +1 or -1, got {direction}")
+    if col0 < 0 or cols <= 0 or col0 + cols > width:
+        raise ValueError(f"seq_shift_rows: columns {col0} .. {col0 + cols} of a matrix {width} wide")
+    if offsets_t.dtype != torch.int64 or offsets_t.dim() != 1 or offsets_t.numel() < 2 or not offsets_t.is_contiguous():
+        raise ValueError("seq_shift_rows: offsets_t must be a contiguous int64 vector of V + 1 entries")
+    if offsets_t.device != src.device:
+        raise ValueError("seq_shift_rows: src and offsets_t must be on the same device")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or out.shape != (rows, cols) or not out.is_contiguous():
+        raise ValueError(f"seq_shift_rows: out must be a contiguous float32 [{rows}, {cols}]")
+    check(lib().avs_seq_shift_rows_f32(_p(src), src.stride(0) if rows > 1 else width, col0, cols, rows, _p(offsets_t),
+                                       offsets_t.numel() - 1, direction, _p(out), cols, _stream()),
+          "avs_seq_shift_rows_f32")
+    return out
+
+
+class _SeqMse(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, targets, table):
+        stride = 0 if targets.shape[0] == table.nseq else 1   # (V == R, every video one row: both forms are one vector)
+        losses = torch.empty(table.nseq, dtype=torch.float32, device=scores.device)
+        check(lib().avs_seq_mse_f32(_p(scores), _p(targets), stride, table.rows, _p(table.offsets_t), table.nseq,
+                                    _p(losses), _stream()), "avs_seq_mse_f32")
+        ctx.table, ctx.stride = table, stride
+        ctx.save_for_backward(scores, targets)
+        return losses
+
+    @staticmethod
+    def backward(ctx, dlosses):
+        scores, targets = ctx.saved_tensors
+        table = ctx.table
+        dlosses = dlosses.contiguous().float()
+        dscores = torch.empty_like(scores)
+        check(lib().avs_seq_mse_bwd_f32(_p(dlosses), _p(scores), _p(targets), ctx.stride, table.rows, _p(table.offsets_t),
+                                        table.nseq, table.max_t, _p(dscores), _stream()), "avs_seq_mse_bwd_f32")
+        return dscores, None, None
+
+
+def seq_mse(scores, targets, offsets):
+    """Per-video mean squared error of a ragged batch: fp32 [V], losses[v] = mean over the rows of video v of
+    (scores - target)^2, differentiable with respect to ``scores`` (dscores[r] = dlosses[v] * (2 / T_v) * (p_r - y)).
+    The sum runs in fp64 in an order that depends on the video's length alone and is rounded once: a video's loss is the
+    same bits alone and in any batch.  ``scores`` fp32 [R] device; ``targets`` fp32 device, [V] (one broadcast target
+    per video, what F.mse_loss against the reference's single shot score computes) or [R] (one per row); ``offsets``:
+    host array-like [V + 1] or an ops.SeqTable.  The batch loss of a step is ``seq_mse(...).mean()``: its gradient is the
+    average of the per-video gradients, what dist.allreduce_gradients gives V ranks that take one video each."""
+    _eval_vector(scores, "scores", "seq_mse", (torch.float32,))
+    _eval_vector(targets, "targets", "seq_mse", (torch.float32,))
+    if targets.device != scores.device:
+        raise ValueError("seq_mse: scores and targets must be on the same device")
+    table = _seq_table(offsets, scores.shape[0], scores.device, "seq_mse")
+    if targets.shape[0] not in (table.nseq, table.rows):
+        raise ValueError(f"seq_mse: targets must hold one entry per video ({table.nseq}) or per row ({table.rows}), got "
+                         f"{targets.shape[0]}")
+    return _SeqMse.apply(scores, targets, table)

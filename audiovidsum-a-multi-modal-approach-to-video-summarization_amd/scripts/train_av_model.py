@@ -7,6 +7,10 @@ forward/backward run through libavsum_hip.so; the loss, the optimiser and the da
 torch, exactly as in the reference.  ``train()`` reads the TVSum HDF5 annotations like the reference and needs
 h5py + the dataset on disk; ``train_synthetic`` is the BASELINE config-5 harness (synthetic labels ~U[1,5]).
 With torch.distributed initialised (one process per GPU) the gradients are all-reduced before each step.
+
+``train_on_dataset(..., videos_per_step=k)`` with k in 2..8 trains on k of the eight videos the loader draws, as ONE ragged
+batch per optimiser step (``collate_videos`` -> ``train_step_batch``: AVBiLSTMModel.train_rows, ops.seq_mse, the mean
+of the per-video losses).  The default k = 1 is the reference's loop, untouched.
 """
 import torch
 import torch.nn.functional as F
@@ -33,13 +37,77 @@ def train_step(model, optimizer, features, frame_scores, device="cuda"):
     return float(loss.item())
 
 
-def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, device="cuda"):
+def collate_videos(items):
+    """Host only (torch on the CPU): V dataset items ({"visual": [S_v, Dv], "audio": [S_v, Da]}, frame scores) as one
+    ragged batch -> (visual_rows fp32 [R, Dv], audio_rows fp32 [R, Da], offsets int64 [V + 1], targets fp32 [V]).
+    targets[v] is the target train_step builds for that video: the single shot score of the boundary (0, S_v) at fps 30.
+    Refused with a ValueError: no item, a video without shots, visual / audio of different lengths, feature widths that
+    differ between the videos."""
+    if len(items) == 0:
+        raise ValueError("collate_videos: no video")
+    vis, aud, lengths, targets = [], [], [], []
+    for i, (features, frame_scores) in enumerate(items):
+        v, a = features["visual"], features["audio"]
+        if v.dim() != 2 or a.dim() != 2 or v.shape[0] != a.shape[0]:
+            raise ValueError(f"collate_videos: video {i} has visual {tuple(v.shape)} and audio {tuple(a.shape)}")
+        if v.shape[0] == 0:
+            raise ValueError(f"collate_videos: video {i} is empty")
+        if vis and (v.shape[1] != vis[0].shape[1] or a.shape[1] != aud[0].shape[1]):
+            raise ValueError(f"collate_videos: video {i} has feature widths {v.shape[1]} / {a.shape[1]}, video 0 "
+                             f"{vis[0].shape[1]} / {aud[0].shape[1]}")
+        shot_scores = align_shots_to_annotations(shot_boundaries=[(0, v.shape[0])], annotations=frame_scores.numpy(),
+                                                 fps=30)
+        vis.append(v.float())
+        aud.append(a.float())
+        lengths.append(v.shape[0])
+        targets.append(shot_scores.float().reshape(1))
+    offsets = torch.zeros(len(items) + 1, dtype=torch.int64)
+    offsets[1:] = torch.cumsum(torch.tensor(lengths, dtype=torch.int64), 0)
+    return torch.cat(vis), torch.cat(aud), offsets, torch.cat(targets)
+
+
+def train_step_batch(model, optimizer, items, device="cuda"):
+    """One optimiser step on V videos at once: one upload of the collated rows, one forward / backward over the ragged
+    batch, the loss = the mean of the per-video MSEs - its gradient is the average of the per-video gradients, i.e.
+    what V ranks that take one video each hold after dist.allreduce_gradients (the same step up to summation order).
+    Returns the per-video losses (a list of floats) from ONE download, after the step."""
+    visual, audio, offsets, targets = collate_videos(items)
+    table = ops.SeqTable(offsets, visual.shape[0], device)
+    preds = model.train_rows(visual.to(device), audio.to(device), table)
+    losses = ops.seq_mse(preds, targets.to(device), table)
+    loss = losses.mean()
+    optimizer.zero_grad()
+    loss.backward()
+    avd.allreduce_gradients(model)
+    optimizer.step()
+    return losses.detach().cpu().tolist()
+
+
+def select_items(items, rank, world, videos_per_step):
+    """The videos of one drawn batch that this rank trains on: positions (rank + j * world) % len(items) for
+    j < videos_per_step, duplicates dropped (a short last batch yields fewer)."""
+    picked = []
+    for j in range(videos_per_step):
+        i = (rank + j * world) % len(items)
+        if i not in picked:
+            picked.append(i)
+    return [items[i] for i in picked]
+
+
+def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, device="cuda", videos_per_step=1):
     """One process: the reference's loop exactly (its DataLoader, its global-RNG shuffle, item 0 of every batch of 8).
     With torch.distributed initialised (one process per GPU) it is data-parallel over that loop: rank 0's weights are
     broadcast first (C1), every rank draws the SAME shuffled batches of 8 (the shuffle seed comes from rank 0) and
     takes item `rank` of each (rank 0 the item the reference would take), gradients are averaged (C3) before every
-    AdamW step - so the replicas and their optimiser states stay identical."""
+    AdamW step - so the replicas and their optimiser states stay identical.
+
+    videos_per_step = k in 2..8: every optimiser step trains on k videos of the drawn batch of 8 as one ragged batch
+    (train_step_batch) - positions (rank + j * world) % len(batch), j < k, duplicates dropped; k = 8 in one process
+    uses every video the loader draws.  on_step then receives the mean of the step's per-video losses.  Dropout draws
+    its masks for the whole batch at once, so torch's RNG is consumed differently from k one-video steps."""
     import torch.distributed as tdist
+    if not isinstance(videos_per_step, int) or not 1 <= videos_per_step <= 8:
+        raise ValueError(f"videos_per_step must be 1..8 (the loader draws batches of 8), got {videos_per_step!r}")
     model = (model or AVBiLSTMModel()).to(device)
     rank, world, gen = 0, 1, None
     if tdist.is_initialized() and tdist.get_world_size() > 1:
@@ -48,15 +116,24 @@ def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, dev
         seed = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int64).to(device)
         tdist.broadcast(seed, 0)
         gen = torch.Generator().manual_seed(int(seed.item()))
-    loader = DataLoader(dataset, batch_size=8, shuffle=True, generator=gen,
-                        collate_fn=lambda items: items[rank % len(items)])
+    if videos_per_step == 1:
+        collate = lambda items: items[rank % len(items)]  # noqa: E731
+    else:
+        collate = lambda items: select_items(items, rank, world, videos_per_step)  # noqa: E731
+    loader = DataLoader(dataset, batch_size=8, shuffle=True, generator=gen, collate_fn=collate)
     optimizer = torch.optim.AdamW(model.parameters(), lr=lr)
     for _ in range(epochs):
         model.train()
-        for features, frame_scores in loader:
-            loss = train_step(model, optimizer, features, frame_scores, device)
-            if on_step is not None:
-                on_step(loss)
+        if videos_per_step == 1:
+            for features, frame_scores in loader:
+                loss = train_step(model, optimizer, features, frame_scores, device)
+                if on_step is not None:
+                    on_step(loss)
+        else:
+            for items in loader:
+                losses = train_step_batch(model, optimizer, items, device)
+                if on_step is not None:
+                    on_step(sum(losses) / len(losses))
         # the recurrences run split over four CUs (ops.lstm*): no bounded wait may have run out during the epoch
         dev = next(model.parameters()).device
         if dev.type == "cuda":

@@ -773,6 +773,32 @@ int avs_rank_pair_counts(const float* d_pred, const void* d_target, int target_b
 int avs_eval_fold(const int32_t* d_counts, const uint8_t* d_mask_pred, const uint8_t* d_mask_target, int64_t rows,
                   const int64_t* d_offsets, int nseg, int max_t, int64_t* d_out, avs_stream_t stream);
 
+/* ---- batched training: a ragged batch of V videos per optimiser step -------------------------------------------------
+ * (scripts/train_av_model.py:86-96 for several videos at once.)  The videos are the segments [offsets[v], offsets[v + 1])
+ * of concatenated rows; d_offsets is int64 [nseq + 1], starts at 0, increases and ends at `rows` (trusted: ops.SeqTable
+ * guarantees it; rows outside every segment are still never read out of bounds).  The recurrences themselves already
+ * take such a table (avs_lstm_*_f32's d_seq_rows); these are the two other places that must know where a video ends.
+ * No float atomics; no entry point synchronises or reads a result back.                                               */
+
+/* d_out[r, 0:cols] = d_src[r - direction, col0 : col0 + cols] when row r - direction lies in the same segment as r, else
+ * 0.  direction +1: the previous row (h_{t-1} of a forward recurrence from its outputs h_t), -1: the next row (of a
+ * reverse recurrence).  Exact copies.                                                                                 */
+int avs_seq_shift_rows_f32(const float* d_src, int64_t ld_src, int col0, int cols, int64_t rows,
+                           const int64_t* d_offsets, int nseq, int direction, float* d_out, int64_t ld_out,
+                           avs_stream_t stream);
+
+/* d_losses[v] = float(sum_r (double(p_r) - double(y_r))^2 / T_v) over the rows of video v: the sum in fp64 in an order
+ * that depends on T_v alone (a video's loss is the same bits wherever it sits in the batch), one rounding to fp32.
+ * target_stride 0: d_targets is [nseq], one target per video (the broadcast target of scripts/train_av_model.py:77-92);
+ * 1: d_targets is [rows], one per row.  One workgroup per video.                                                      */
+int avs_seq_mse_f32(const float* d_scores, const float* d_targets, int target_stride, int64_t rows,
+                    const int64_t* d_offsets, int nseq, float* d_losses, avs_stream_t stream);
+/* d_dscores[r] = (d_dlosses[v] * (2 / T_v)) * (p_r - y_r) in fp32 for the rows of video v; max_t = the longest video
+ * (it sizes the grid).                                                                                                */
+int avs_seq_mse_bwd_f32(const float* d_dlosses, const float* d_scores, const float* d_targets, int target_stride,
+                        int64_t rows, const int64_t* d_offsets, int nseq, int max_t, float* d_dscores,
+                        avs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
