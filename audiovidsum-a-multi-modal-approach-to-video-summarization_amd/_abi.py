@@ -154,6 +154,10 @@ _SIGNATURES = {
     "avs_seq_shift_rows_f32": (c_int, [P, c_int64, c_int, c_int, c_int64, P, c_int, c_int, P, c_int64, P]),
     "avs_seq_mse_f32": (c_int, [P, P, c_int, c_int64, P, c_int, P, P]),
     "avs_seq_mse_bwd_f32": (c_int, [P, P, P, c_int, c_int64, P, c_int, c_int, P, P]),
+    "avs_hsv_frame_diff_batch_u8": (c_int, [P, c_int64, c_int, c_int, c_int, P, c_int, P, P]),
+    "avs_shot_cuts_batch": (c_int, [P, c_int64, P, c_int, c_double, c_double, c_int, P, P, P, P]),
+    "avs_shot_tables_fill": (c_int, [P, c_int, P, P, P, P, P, c_int64, P, P, c_int64, P, c_int64, P, P]),
+    "avs_gather_rows_u8": (c_int, [P, c_int64, c_int64, P, P, c_int64, P, P]),
 }
 
 _lib = None

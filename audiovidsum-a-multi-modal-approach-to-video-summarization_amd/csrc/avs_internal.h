@@ -168,6 +168,29 @@ template <> struct avs_elem<avs_bf16_tag> {
   static __device__ __forceinline__ void store(avs_bf16_tag* p, float v) { p->bits = avs_f32_to_bf16(v); }
 };
 
+// ---- OpenCV's 8-bit BGR -> HSV (H in [0,180), 12-bit fixed-point division tables) [3P-memory: cv2 sources absent
+// here]: the pixel arithmetic of the shot-boundary scans (visual.hip per video, shots_batch.hip per batch).
+__device__ __forceinline__ int cv_round_div(int num_shifted, double den) { return (int)rint((double)num_shifted / den); }
+
+__device__ __forceinline__ void bgr2hsv_u8(int b, int g, int r, int& h, int& s, int& v) {
+  v = max(b, max(g, r));
+  const int vmin = min(b, min(g, r));
+  const int diff = v - vmin;
+  const int sdiv = v > 0 ? cv_round_div(255 << 12, 1.0 * v) : 0;
+  const int hdiv = diff > 0 ? cv_round_div(180 << 12, 6.0 * diff) : 0;
+  s = (diff * sdiv + (1 << 11)) >> 12;
+  int hh;
+  if (v == r)
+    hh = g - b;
+  else if (v == g)
+    hh = b - r + 2 * diff;
+  else
+    hh = r - g + 4 * diff;
+  hh = (hh * hdiv + (1 << 11)) >> 12;
+  if (hh < 0) hh += 180;
+  h = hh;
+}
+
 __device__ __forceinline__ float avs_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -877,28 +877,8 @@ extern "C" int avs_segment_mean_f32(const float* d_x, int64_t ldx, int d, const 
 // (H in [0,180), 12-bit fixed-point division tables) [3P-memory: cv2 / scenedetect sources absent here].
 // Integer arithmetic end to end (block reduction by wave shuffle, one integer atomic per block), so the sums are
 // exact and order-independent.  `step` = PySceneDetect's downscale stride (frame[::step, ::step]).
+// bgr2hsv_u8 lives in avs_internal.h: shots_batch.hip's batched form of this kernel shares it.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int cv_round_div(int num_shifted, double den) { return (int)rint((double)num_shifted / den); }
-
-__device__ __forceinline__ void bgr2hsv_u8(int b, int g, int r, int& h, int& s, int& v) {
-  v = max(b, max(g, r));
-  const int vmin = min(b, min(g, r));
-  const int diff = v - vmin;
-  const int sdiv = v > 0 ? cv_round_div(255 << 12, 1.0 * v) : 0;
-  const int hdiv = diff > 0 ? cv_round_div(180 << 12, 6.0 * diff) : 0;
-  s = (diff * sdiv + (1 << 11)) >> 12;
-  int hh;
-  if (v == r)
-    hh = g - b;
-  else if (v == g)
-    hh = b - r + 2 * diff;
-  else
-    hh = r - g + 4 * diff;
-  hh = (hh * hdiv + (1 << 11)) >> 12;
-  if (hh < 0) hh += 180;
-  h = hh;
-}
-
 __global__ __launch_bounds__(256) void hsv_frame_diff_kernel(const uint8_t* __restrict__ frames, int h, int w,
                                                              int step, int ph, int pw, unsigned* __restrict__ sums) {
   __shared__ unsigned red[4][3];

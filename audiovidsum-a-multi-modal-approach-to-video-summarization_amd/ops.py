@@ -18,6 +18,7 @@ __all__ = [
     "clamp_topdb", "stft_mel_max", "stft_mel_segmean", "stft_mel_segmean_batch", "stft_mel_shots", "vggish_examples", "fill", "quantize", "resample", "lstm", "mha_batchaxis", "score_head", "mhsa_flash", "softmax_rows", "cdist", "dtw_path",
     "gather_scale", "FusionTables", "fusion_batch", "EvalTables", "eval_counts", "segment_mean_mask", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
     "SeqTable", "seq_shift_rows", "seq_mse",
+    "ShotTables", "hsv_frame_diff_batch", "shot_cuts_batch", "shot_tables", "gather_rows",
 ]
 
 
@@ -1811,3 +1812,176 @@ def seq_mse(scores, targets, offsets):
         raise ValueError(f"seq_mse: targets must hold one entry per video ({table.nseq}) or per row ({table.rows}), got "
                          f"{targets.shape[0]}")
     return _SeqMse.apply(scores, targets, table)
+
+
+# --------------------------------------------------------------------------- batched shot detection and sampling
+SHOT_INTERVAL = 3        # features/extractors.py FRAME_INTERVAL: the sampled frames are the multiples of 3,
+SHOT_MAX_FRAMES = 100    # MAX_FRAMES: at most 100 per shot,
+SHOT_MICRO_BATCH = 4     # MICRO_BATCH: in BatchNorm groups of 4 with a shorter tail group
+
+
+class ShotTables:
+    """The host plan of one batch layout for the batched shot detector, built once from the host frame offsets [V + 1]
+    of the videos in the concatenated frames (video v is frames offsets[v] .. offsets[v + 1]) and ``min_scene_len``.
+
+    Host side (numpy): ``offsets``, ``lengths``, ``nvideos``, ``frames`` (= offsets[-1]), ``min_scene_len``, ``cut_off``
+    int64 [V + 1] (video v's slot of the cut buffer: (n_v - 1) // min_scene_len entries, the most the greedy rule can
+    place) and the capacities, all from the offsets alone: ``cut_cap``, ``shot_cap`` = sum of (slot + 1), ``sample_cap``
+    = sum of ceil(n_v / 3) (the shots of a video tile it, so they hold at most its multiples of 3) and ``group_cap`` =
+    sum of (ceil(n_v / 3) // 4 + slot + 1) (sum of ceil(c / 4) <= (F + 3 S) / 4 <= F // 4 + S in integers).  Device side:
+    ``offsets_t``, ``cut_off_t``.  ``device="cpu"`` keeps everything on the host (the builder can be checked without a
+    GPU).  Refused, each with a ValueError: an empty batch, offsets that do not start at 0 or do not increase strictly
+    (an empty video), more than 2^24 frames (the frame is on grid x in workgroups of 256, and a launch holds fewer than
+    2^32 threads per grid dimension), min_scene_len < 1."""
+
+    def __init__(self, offsets_host, min_scene_len=15, device=None):
+        if isinstance(offsets_host, torch.Tensor):
+            if offsets_host.is_cuda:
+                raise ValueError("ShotTables: the offsets are a HOST array (they are validated before the upload)")
+            offsets_host = offsets_host.numpy()
+        off = np.array(offsets_host, dtype=np.int64).reshape(-1)
+        if off.size < 2:
+            raise ValueError("ShotTables: offsets must hold V + 1 entries for V >= 1 videos (the batch is empty)")
+        if off[0] != 0:
+            raise ValueError(f"ShotTables: offsets must start at 0, got {int(off[0])}")
+        n = np.diff(off)
+        if (n <= 0).any():
+            raise ValueError("ShotTables: the offsets must ascend strictly (a video is empty or the offsets decrease)")
+        if off[-1] > 1 << 24:
+            raise ValueError(f"ShotTables: {int(off[-1])} frames, one launch takes at most 2^24")
+        if int(min_scene_len) < 1:
+            raise ValueError(f"ShotTables: min_scene_len must be >= 1, got {min_scene_len}")
+        self.offsets, self.lengths, self.nvideos, self.frames = off, n, int(n.size), int(off[-1])
+        self.min_scene_len = int(min_scene_len)
+        slots = (n - 1) // self.min_scene_len
+        thirds = -(-n // SHOT_INTERVAL)
+        self.cut_off = np.concatenate([[0], np.cumsum(slots)]).astype(np.int64)
+        self.cut_cap = int(slots.sum())
+        self.shot_cap = int((slots + 1).sum())
+        self.sample_cap = int(thirds.sum())
+        self.group_cap = int((thirds // SHOT_MICRO_BATCH + slots + 1).sum())
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.offsets_t = torch.from_numpy(off).to(torch.device(device))
+        self.device = self.offsets_t.device
+        self.cut_off_t = torch.from_numpy(self.cut_off).to(self.device)
+
+
+def _shot_tables_arg(tables, what):
+    if not isinstance(tables, ShotTables):
+        raise ValueError(f"{what}: tables must be an ops.ShotTables")
+    if not tables.device.type == "cuda":
+        raise ValueError(f"{what}: the tables are on the host (there is no CPU fallback)")
+
+
+def _i64_vector(t, name, what, device, numel=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{what}: {name} must be a device tensor (there is no CPU fallback)")
+    if t.dtype != torch.int64 or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise ValueError(f"{what}: {name} must be a contiguous int64 tensor" + (f" of {numel} entries" if numel else ""))
+    if t.device != device:
+        raise ValueError(f"{what}: {name} is on {t.device}, the tables on {device}")
+
+
+def hsv_frame_diff_batch(frames_u8, tables, step=1, raw=False):
+    """frames uint8 [N,h,w,3] on device, the videos of ``tables`` concatenated -> int64 [N,3] sums of |dH|,|dS|,|dV|
+    against the previous frame of the same video: row for row the integers of one hsv_frame_diff call per video (zeros
+    at every video's first frame), in one launch and with N not limited to 65 536.  raw=True returns the int32 [N,3]
+    buffer of uint32 bit patterns the kernel wrote (what shot_cuts_batch reads)."""
+    _shot_tables_arg(tables, "hsv_frame_diff_batch")
+    if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda:
+        raise ValueError("hsv_frame_diff_batch: frames must be a device tensor (there is no CPU fallback)")
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
+        raise ValueError("hsv_frame_diff_batch: frames must be contiguous uint8 [n,h,w,3]")
+    n, h, w, _ = frames_u8.shape
+    if n != tables.frames or frames_u8.device != tables.device:
+        raise ValueError(f"hsv_frame_diff_batch: {n} frames on {frames_u8.device}, the tables hold {tables.frames} on "
+                         f"{tables.device}")
+    if int(step) < 1:
+        raise ValueError(f"hsv_frame_diff_batch: step must be >= 1, got {step}")
+    sums = torch.empty((n, 3), dtype=torch.int32, device=frames_u8.device)
+    check(lib().avs_hsv_frame_diff_batch_u8(_p(frames_u8), n, h, w, int(step), _p(tables.offsets_t), tables.nvideos,
+                                            _p(sums), _stream()), "avs_hsv_frame_diff_batch_u8")
+    return sums if raw else sums.to(torch.int64) & 0xFFFFFFFF
+
+
+def shot_cuts_batch(tables, sums, pixels, threshold=27.0):
+    """features.shots.content_scores + cuts_from_scores of every video of ``tables`` in one launch.  ``sums``: the int32
+    [N,3] buffer of hsv_frame_diff_batch(..., raw=True); ``pixels``: the strided pixel count the sums run over.  Returns
+    (cuts int64 [cut_cap]: video v's cuts, video-relative and ascending, from tables.cut_off[v], the rest of its slot
+    not written; totals int64 [V,4] = per video (shots, sampled frames, micro-batch groups, most sampled frames of a shot)), both on the device.  The
+    threshold decision is the host's fp64 decision bit for bit; tables.min_scene_len is the greedy rule's gap."""
+    _shot_tables_arg(tables, "shot_cuts_batch")
+    if not isinstance(sums, torch.Tensor) or not sums.is_cuda:
+        raise ValueError("shot_cuts_batch: sums must be a device tensor (there is no CPU fallback)")
+    if sums.dtype != torch.int32 or tuple(sums.shape) != (tables.frames, 3) or not sums.is_contiguous():
+        raise ValueError(f"shot_cuts_batch: sums must be the contiguous int32 [{tables.frames}, 3] buffer of "
+                         "hsv_frame_diff_batch(..., raw=True)")
+    if sums.device != tables.device:
+        raise ValueError("shot_cuts_batch: sums and tables must be on the same device")
+    if not float(pixels) > 0:
+        raise ValueError(f"shot_cuts_batch: pixels must be positive, got {pixels}")
+    cuts = torch.empty(max(tables.cut_cap, 1), dtype=torch.int64, device=tables.device)
+    totals = torch.empty((tables.nvideos, 4), dtype=torch.int64, device=tables.device)
+    check(lib().avs_shot_cuts_batch(_p(sums), tables.frames, _p(tables.offsets_t), tables.nvideos, float(pixels),
+                                    float(threshold), tables.min_scene_len, _p(tables.cut_off_t), _p(cuts), _p(totals),
+                                    _stream()), "avs_shot_cuts_batch")
+    return cuts[:tables.cut_cap], totals
+
+
+def shot_tables(tables, cuts, totals):
+    """The shot, sample and micro-batch tables of every video from shot_cuts_batch's ``cuts`` and ``totals``: a
+    one-workgroup scan and one workgroup per video, nothing read back.  Returns a dict of device tensors at their
+    CAPACITIES (tables.shot_cap / sample_cap / group_cap; the entries past the counts are not written):
+      counts int64 [4] = (S, F, G, most sampled frames of a shot); shot_offsets int64 [V + 1]; shots int64 [shot_cap, 2]
+      (video-relative (start, end), the tuples of detect_shots); sample_offsets int64 [shot_cap + 1] (entry S = F);
+      sample_index int64 [sample_cap] (rows of the concatenated frames); group_offsets int64 [group_cap + 1] (rows of the
+      sampled tensor, entry G = F); packed: the int64 buffer all of them but sample_index are views of (ONE download
+      brings every table a host needs)."""
+    _shot_tables_arg(tables, "shot_tables")
+    _i64_vector(cuts, "cuts", "shot_tables", tables.device, tables.cut_cap)
+    _i64_vector(totals, "totals", "shot_tables", tables.device, tables.nvideos * 4)
+    nv, dev = tables.nvideos, tables.device
+    sizes = (4, 3 * (nv + 1), 2 * tables.shot_cap, tables.shot_cap + 1, tables.group_cap + 1)
+    packed = torch.empty(sum(sizes), dtype=torch.int64, device=dev)
+    counts, video_off, shots, sample_offsets, group_offsets = torch.split(packed, sizes)
+    sample_index = torch.empty(max(tables.sample_cap, 1), dtype=torch.int64, device=dev)
+    cuts_arg = cuts if cuts.numel() else torch.empty(1, dtype=torch.int64, device=dev)   # (never read: every slot is empty)
+    check(lib().avs_shot_tables_fill(_p(tables.offsets_t), nv, _p(tables.cut_off_t), _p(cuts_arg), _p(totals), _p(video_off),
+                                     _p(shots), tables.shot_cap, _p(sample_offsets), _p(sample_index), tables.sample_cap,
+                                     _p(group_offsets), tables.group_cap, _p(counts), _stream()), "avs_shot_tables_fill")
+    return {"counts": counts, "shot_offsets": video_off[:nv + 1], "shots": shots.view(tables.shot_cap, 2),
+            "sample_offsets": sample_offsets, "sample_index": sample_index[:tables.sample_cap],
+            "group_offsets": group_offsets, "packed": packed}
+
+
+def gather_rows(src, index, count, out=None):
+    """out[i] = src[index[i]] for i < count, rows of any dtype and shape copied as bytes.  ``src`` [R, ...] contiguous
+    device tensor; ``index`` int64 device vector [capacity] of rows of src; ``count`` an int64 device tensor of ONE
+    element: the row count is read on the device (no download sizes the launch - the grid covers the capacity and the
+    surplus workgroups exit).  ``out`` [capacity, ...] (allocated when None); rows from ``count`` on are left as they
+    were.  An index outside src is skipped.  capacity < 2^24."""
+    for t, name in ((src, "src"), (index, "index"), (count, "count")) + (((out, "out"),) if out is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"gather_rows: {name} must be a device tensor (there is no CPU fallback)")
+    if src.dim() < 1 or not src.is_contiguous():
+        raise ValueError("gather_rows: src must be a contiguous tensor of rows")
+    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
+        raise ValueError("gather_rows: index must be a contiguous int64 vector")
+    if count.dtype != torch.int64 or count.numel() != 1:
+        raise ValueError("gather_rows: count must be an int64 tensor of one element")
+    if index.device != src.device or count.device != src.device:
+        raise ValueError("gather_rows: src, index and count must be on the same device")
+    cap = index.numel()
+    row_shape = tuple(src.shape[1:])
+    row_bytes = int(np.prod(row_shape, dtype=np.int64)) * src.element_size()
+    if row_bytes <= 0:
+        raise ValueError(f"gather_rows: rows of shape {row_shape} are empty")
+    if out is None:
+        out = torch.empty((cap,) + row_shape, dtype=src.dtype, device=src.device)
+    elif out.dtype != src.dtype or tuple(out.shape) != (cap,) + row_shape or not out.is_contiguous() or \
+            out.device != src.device:
+        raise ValueError(f"gather_rows: out must be a contiguous {src.dtype} tensor of shape {(cap,) + row_shape}")
+    check(lib().avs_gather_rows_u8(_p(src), src.shape[0], row_bytes, _p(index), _p(count), cap, _p(out), _stream()),
+          "avs_gather_rows_u8")
+    return out

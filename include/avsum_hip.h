@@ -799,6 +799,51 @@ int avs_seq_mse_bwd_f32(const float* d_dlosses, const float* d_scores, const flo
                         int64_t rows, const int64_t* d_offsets, int nseq, int max_t, float* d_dscores,
                         avs_stream_t stream);
 
+/* ---- batched shot detection and frame sampling: the front half of stage 1 for V videos per call ----------------------
+ * (features/shots.py and the sampling loop of features/extractors.py.)  The videos are the segments [offsets[v],
+ * offsets[v + 1]) of the concatenated frames; d_offsets is int64 [nvideos + 1], starts at 0, increases strictly and ends
+ * at n (trusted: ops.ShotTables guarantees it).  Integers and fixed orders only, so two calls on the same input give
+ * the same bytes.  No entry point synchronises or reads a result back.                                                */
+
+/* d_sums uint32 [n, 3]: per frame the sums of |dH|, |dS|, |dV| against the previous frame of the SAME video - the
+ * integers of one avs_hsv_frame_diff_u8 call per video; the first frame of every video gets zeros.  The frame is on
+ * grid x: n is bounded by 2^24 = 16 777 216 (a launch holds at most 2^32 - 1 threads per grid dimension, in workgroups
+ * of 256), not by 65 536.                                                                                             */
+int avs_hsv_frame_diff_batch_u8(const uint8_t* d_frames, int64_t n, int h, int w, int step, const int64_t* d_offsets,
+                                int nvideos, uint32_t* d_sums, avs_stream_t stream);
+
+/* Every video's cut list, one workgroup per video: frame f >= 1 is flagged when ((s0/p + s1/p) + s2/p) / 3.0 >=
+ * threshold in fp64 (p = pixels, the strided pixel count; the host's expression and so the host's decision bit for
+ * bit), and is a cut when it is the first flagged frame with f - last >= min_scene_len (last = the previous cut, 0
+ * before the first).  Video v's cuts (video-relative frames, ascending) go to d_cuts[d_cut_off[v] ...]; d_cut_off is
+ * int64 [nvideos + 1], the exclusive scan of the slot sizes (n_v - 1) / min_scene_len - the most the rule can place.
+ * The rest of a slot is not written; a slot that is full ends the video's cuts (no store leaves the slot).
+ * d_totals int64 [nvideos, 4] = (shots: 0 without a cut, else cuts + 1; sampled frames; micro-batch groups of 4; the
+ * most sampled frames of one shot), a shot (s, e) holding min(100, ceil(e/3) - ceil(s/3)) sampled frames.             */
+int avs_shot_cuts_batch(const uint32_t* d_sums, int64_t n, const int64_t* d_offsets, int nvideos, double pixels,
+                        double threshold, int min_scene_len, const int64_t* d_cut_off, int64_t* d_cuts,
+                        int64_t* d_totals, avs_stream_t stream);
+
+/* The tables, from the cuts and totals above: a one-workgroup scan of the totals, then one workgroup per video.
+ * d_video_off int64 [3, nvideos + 1]: the exclusive scans of (shots, sampled frames, groups) per video; plane 0 is the
+ * shot_offsets table.  d_shots int64 [S, 2]: video-relative (start, end).  d_sample_offsets int64 [S + 1]: first row
+ * of each shot in the sampled tensor.  d_sample_index int64 [F]: rows of the concatenated frames, frame k of shot
+ * (s, e) of video v being offsets[v] + 3 (ceil(s/3) + k).  d_group_offsets int64 [G + 1]: rows of the sampled tensor,
+ * each shot cut into groups of 4 with a shorter tail group.  d_counts int64 [4] = (S, F, G, most frames of a shot).
+ * The capacities are those of the buffers (S + 1 <= shot_cap + 1 entries of d_sample_offsets, ...); nothing is written
+ * past them.                                                                                                          */
+int avs_shot_tables_fill(const int64_t* d_offsets, int nvideos, const int64_t* d_cut_off, const int64_t* d_cuts,
+                         const int64_t* d_totals, int64_t* d_video_off, int64_t* d_shots, int64_t shot_cap,
+                         int64_t* d_sample_offsets, int64_t* d_sample_index, int64_t sample_cap,
+                         int64_t* d_group_offsets, int64_t group_cap, int64_t* d_counts, avs_stream_t stream);
+
+/* d_out[i] = d_src[d_index[i]] for rows of row_bytes bytes, i < min(*d_count, capacity): the row count is read from
+ * device memory, the grid is sized by `capacity` and rows past the count are left as they were.  16-byte units when
+ * row_bytes % 16 == 0 and both bases are 16-byte aligned, else 4-byte, else single bytes.  An index outside
+ * [0, src_rows) is skipped.  capacity < 2^24 (one workgroup of 256 per row on grid x).                                */
+int avs_gather_rows_u8(const uint8_t* d_src, int64_t src_rows, int64_t row_bytes, const int64_t* d_index,
+                       const int64_t* d_count, int64_t capacity, uint8_t* d_out, avs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
