@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..ragged import exclusive_offsets
 
 
 def _dev():
@@ -105,8 +106,8 @@ def fuse_batch(visuals, audios, target_length):
     aus = [torch.as_tensor(x).float() for x in audios]
     if any(x.dim() != 2 for x in vs + aus):
         raise ValueError("XA must be a 2-dimensional array.")
-    vo = np.concatenate([[0], np.cumsum([x.shape[0] for x in vs])]).tolist()
-    ao = np.concatenate([[0], np.cumsum([x.shape[0] for x in aus])]).tolist()
+    vo = exclusive_offsets([x.shape[0] for x in vs]).tolist()
+    ao = exclusive_offsets([x.shape[0] for x in aus]).tolist()
     tables = fusion_tables(vo, ao, dev)
     fused, _ = fuse_batch_device(torch.cat(vs).contiguous().to(dev), torch.cat(aus).contiguous().to(dev), vo, ao,
                                  target_length, tables=tables)

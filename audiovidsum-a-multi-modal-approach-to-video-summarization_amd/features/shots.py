@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..ragged import exclusive_offsets
 
 DEFAULT_MIN_WIDTH = 256  # scenedetect.scene_manager.DEFAULT_MIN_WIDTH
 
@@ -71,7 +72,7 @@ def shot_tables_host(cuts_per_video, lengths):
     lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
     if len(cuts_per_video) != lengths.size:
         raise ValueError("shot_tables_host: one cut list per video")
-    base = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    base = exclusive_offsets(lengths)
     starts, ends, video, per_video = [], [], [], []
     for v, (cuts, n) in enumerate(zip(cuts_per_video, lengths)):
         cuts = np.asarray(cuts, dtype=np.int64).reshape(-1)
@@ -86,14 +87,13 @@ def shot_tables_host(cuts_per_video, lengths):
     first = -(-start // ops.SHOT_INTERVAL)                                  # ceil(s / 3)
     count = np.minimum(ops.SHOT_MAX_FRAMES, -(-end // ops.SHOT_INTERVAL) - first)
     groups = -(-count // ops.SHOT_MICRO_BATCH)
-    ex = lambda x: np.concatenate([[0], np.cumsum(x)]).astype(np.int64)      # exclusive prefix sums (+ the total)
-    sample_offsets, group_first = ex(count), ex(groups)
+    sample_offsets, group_first = exclusive_offsets(count), exclusive_offsets(groups)
     nsample, ngroup = int(sample_offsets[-1]), int(group_first[-1])
     k = np.arange(nsample, dtype=np.int64) - np.repeat(sample_offsets[:-1], count)
     sample_index = np.repeat(base[video] + ops.SHOT_INTERVAL * first, count) + ops.SHOT_INTERVAL * k
     g = np.arange(ngroup, dtype=np.int64) - np.repeat(group_first[:-1], groups)
     group_offsets = np.concatenate([np.repeat(sample_offsets[:-1], groups) + ops.SHOT_MICRO_BATCH * g, [nsample]])
-    return {"shot_offsets": ex(per_video), "shots": np.stack([start, end], 1).reshape(-1, 2),
+    return {"shot_offsets": exclusive_offsets(per_video), "shots": np.stack([start, end], 1).reshape(-1, 2),
             "sample_offsets": sample_offsets, "sample_index": sample_index.astype(np.int64),
             "group_offsets": group_offsets.astype(np.int64),
             "counts": np.array([start.size, nsample, ngroup, int(count.max()) if count.size else 0], dtype=np.int64)}
@@ -117,8 +117,7 @@ class ShotBatchResult:
         if self._host is None:
             nv, plan = self.plan.nvideos, self.plan
             flat = self._packed.cpu().numpy()
-            sizes = (4, 3 * (nv + 1), 2 * plan.shot_cap, plan.shot_cap + 1, plan.group_cap + 1)
-            counts, video_off, shots, sample_offsets, group_offsets = np.split(flat, np.cumsum(sizes)[:-1])
+            counts, video_off, shots, sample_offsets, group_offsets = np.split(flat, np.cumsum(plan.packed_sizes)[:-1])
             s, f, g, _ = (int(x) for x in counts)
             if s > plan.shot_cap or f > plan.sample_cap or g > plan.group_cap:
                 raise RuntimeError(f"detect_shots_batch: counts {counts.tolist()} exceed the capacities "

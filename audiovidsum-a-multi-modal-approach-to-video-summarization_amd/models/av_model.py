@@ -131,10 +131,7 @@ class AVBiLSTMModel(nn.Module):
             raise ValueError(f"expected visual_rows [R,Dv] and audio_rows [R,Da], got {tuple(visual_rows.shape)} / "
                              f"{tuple(audio_rows.shape)}")
         rows = visual_rows.shape[0]
-        table = offsets if isinstance(offsets, ops.SeqTable) else ops.SeqTable(offsets, rows, visual_rows.device)
-        if table.rows != rows or table.device != visual_rows.device:
-            raise ValueError(f"the offsets end at {table.rows} on {table.device}; the batch has {rows} rows on "
-                             f"{visual_rows.device}")
+        table = ops._seq_table(offsets, rows, visual_rows.device, "train_rows")
         from ._scorer_train import ScorerTrainFunction, dropout_keep
         v = visual_rows.float().contiguous()
         a = audio_rows.float().contiguous()

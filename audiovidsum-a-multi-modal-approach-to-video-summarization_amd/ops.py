@@ -11,6 +11,8 @@ import torch
 from . import _abi
 from ._abi import (ACT_NONE, ACT_RELU, AVS_BF16, AVS_F16X2, AVS_F32, AVS_F32_SPLIT, BIAS_COL, BIAS_NONE, BIAS_ROW, check,
                    lib)
+from .ragged import (EVAL_CHUNK, EVAL_MAX_T, EVAL_TILE, FUSION_MAX_N, FUSION_MID_L, FUSION_SMALL_L,  # noqa: F401
+                     SHOT_INTERVAL, SHOT_MAX_FRAMES, SHOT_MICRO_BATCH, EvalTables, FusionTables, SeqTable, ShotTables)
 
 __all__ = [
     "ACT_NONE", "ACT_RELU", "linear", "gemm_nt_batched", "conv2d", "conv2d_raw", "conv2d_split", "conv_bnlocal_tile_rows", "conv_bncluster_ok", "conv_bnstats_ok", "cluster_exchange_errors", "lstm_split_errors", "conv1x1_bn", "conv1x1_gram_bn", "bn_gram_affine", "gram_supported", "frames_normalize", "pull_copy", "stem_conv_bn_pool", "stem_h2_operands", "stem_conv_pool_h2", "resize_bilinear",
@@ -198,6 +200,40 @@ def _f32(t, name):
 def _rowmajor2d(t, name):
     if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
         raise ValueError(f"{name} must be 2-D with unit column stride, got shape {tuple(t.shape)} strides {t.stride()}")
+
+
+def _device_arg(t, name, what, dtypes=None, ndim=None, shape=None, numel=None, device=None, contiguous=True):
+    """Refuses, with a ValueError that starts with ``what``, an argument ``name`` that is not a device tensor of one of
+    ``dtypes``, of rank ``ndim``, of ``shape`` (None: that extent is free), of ``numel`` elements, contiguous and on
+    ``device``; a constraint left at None is not checked."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{what}: {name} must be a device tensor (there is no CPU fallback)")
+    if dtypes is not None and t.dtype not in dtypes:
+        raise ValueError(f"{what}: {name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if shape is not None and (t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape))):
+        raise ValueError(f"{what}: {name} must have shape {list(shape)} (None: any), got {list(t.shape)}")
+    if (ndim is not None and t.dim() != ndim) or (numel is not None and t.numel() != numel) or \
+            (contiguous and not t.is_contiguous()):
+        raise ValueError(f"{what}: {name} must be a{' contiguous' if contiguous else ''} tensor"
+                         + (f" of rank {ndim}" if ndim is not None else "")
+                         + (f" of {numel} entries" if numel is not None else "")
+                         + f", got shape {list(t.shape)} with strides {list(t.stride())}")
+    if device is not None and t.device != device:
+        raise ValueError(f"{what}: {name} is on {t.device}, the other arguments on {device}")
+
+
+def _tables_arg(tables, cls, what, device=None, rows=None):
+    """Refuses, with a ValueError that starts with ``what``, a ``tables`` that is not a ``cls`` uploaded to a HIP device
+    (to ``device``, where given), or whose offsets do not end at ``rows`` (where given).  Returns ``tables``."""
+    if not isinstance(tables, cls):
+        raise ValueError(f"{what}: tables must be an ops.{cls.__name__}")
+    if tables.device.type != "cuda":
+        raise ValueError(f"{what}: the tables are on the host (there is no CPU fallback)")
+    if device is not None and tables.device != device:
+        raise ValueError(f"{what}: the tables are on {tables.device}, the rows on {device}")
+    if rows is not None and tables.total != rows:
+        raise ValueError(f"{what}: the offsets end at {tables.total}, the batch has {rows} rows")
+    return tables
 
 
 # --------------------------------------------------------------------------- GEMM / conv
@@ -1444,86 +1480,6 @@ def gather_scale(x, idx, w):
 
 
 # --------------------------------------------------------------------------- batched fusion
-FUSION_MAX_N = 6400      # rows of the visual side of one pair (the per-pair limit of dtw_path)
-FUSION_SMALL_L = 64      # size classes by l = min(n, m): l <= 64 one wave per pair (four pairs per workgroup),
-FUSION_MID_L = 512       # l <= 512 one 256-thread workgroup per pair, above that one 1024-thread workgroup
-_FUSION_TILE = 32        # the cost kernel's output tile
-
-
-class FusionTables:
-    """The host plan of one batch layout for fusion_batch, built once from the host list of pairs
-    ``(v_row0, n, a_row0, m)``: pair p is rows v_row0 .. v_row0 + n of the visual matrix against rows a_row0 ..
-    a_row0 + m of the audio matrix.  Nothing is padded; the pairs may leave gaps and come in any order.
-
-    Host side (numpy): ``n``, ``m``, ``cell_off`` (first element of the pair's [n, m] block in the cost buffer and the
-    code workspace), ``path_off`` / ``path_cap`` (its path slot: n + m - 1 rows), ``row_off`` (first of its n row
-    counts), ``cls`` (size class 0/1/2), ``order`` (pairs sorted by class, longest sweep first inside a class),
-    ``class_count``, ``class_max_l``, ``tiles`` (pair, row tile, column tile), ``cells``, ``path_rows``, ``rows``,
-    ``workspace_bytes``.  Device side: ``pairs`` int64 [P, 8], ``order_t``, ``tiles_t``, ``row_pair`` int32 [rows].
-    ``device="cpu"`` keeps everything on the host (the table builder can be checked without a GPU)."""
-
-    def __init__(self, pairs, device=None):
-        arr = np.asarray(list(pairs), dtype=np.int64).reshape(-1, 4)
-        v0, n, a0, m = (arr[:, k].copy() for k in range(4))
-        if (n <= 0).any() or (m <= 0).any():
-            raise ValueError("fusion_batch: a pair is empty (n == 0 or m == 0)")
-        if (v0 < 0).any() or (a0 < 0).any():
-            raise ValueError("fusion_batch: negative row offset")
-        if (n > FUSION_MAX_N).any():
-            raise ValueError(f"fusion_batch: a pair has n = {int(n.max())} rows, above the LDS-resident limit {FUSION_MAX_N}")
-        if (m >= 1 << 30).any():
-            raise ValueError("fusion_batch: a pair has m >= 2^30 rows")
-        npairs = arr.shape[0]
-        self.npairs, self.v_row0, self.n, self.a_row0, self.m = npairs, v0, n, a0, m
-        self.v_rows_needed = int((v0 + n).max()) if npairs else 0
-        self.a_rows_needed = int((a0 + m).max()) if npairs else 0
-        ex = lambda x: np.concatenate([[0], np.cumsum(x)]).astype(np.int64)   # exclusive prefix sums (+ the total)
-        cell, path, row = ex(n * m), ex(n + m - 1), ex(n)
-        self.cell_off, self.path_off, self.row_off = cell[:-1], path[:-1], row[:-1]
-        self.path_cap = n + m - 1
-        self.cells, self.path_rows, self.rows = int(cell[-1]), int(path[-1]), int(row[-1])
-        small = np.minimum(n, m)
-        self.cls = (small > FUSION_SMALL_L).astype(np.int64) + (small > FUSION_MID_L)
-        # by class, then the most anti-diagonals first (neighbours in a class-0 workgroup sweep about as long); stable
-        self.order = np.lexsort((np.arange(npairs), -(n + m), self.cls)).astype(np.int32)
-        self.class_count = [int((self.cls == c).sum()) for c in range(3)]
-        self.class_max_l = [int(small[self.cls == c].max()) if self.class_count[c] else 0 for c in range(3)]
-        self.max_n = int(n.max()) if npairs else 0
-        ti, tj = -(-n // _FUSION_TILE), -(-m // _FUSION_TILE)
-        per = ti * tj
-        self.ntiles = int(per.sum())
-        tp = np.repeat(np.arange(npairs, dtype=np.int64), per)
-        k = np.arange(self.ntiles, dtype=np.int64) - np.repeat(ex(per)[:-1], per)
-        self.tiles = np.stack([tp, k // tj[tp], k % tj[tp]], 1).astype(np.int32).reshape(-1, 3)
-        self.row_pair_host = np.repeat(np.arange(npairs, dtype=np.int32), n)
-        self.workspace_bytes = (self.cells + 255) & ~255     # avs_dtw_batch_workspace_bytes: one code byte per cell
-        table = np.zeros((npairs, 8), dtype=np.int64)
-        for col, x in enumerate((v0, n, a0, m, self.cell_off, self.path_off, self.row_off)):
-            table[:, col] = x
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.pairs = torch.from_numpy(table).to(torch.device(device))
-        self.device = self.pairs.device
-        self.order_t = torch.from_numpy(self.order).to(self.device)
-        self.tiles_t = torch.from_numpy(self.tiles).to(self.device)
-        self.row_pair = torch.from_numpy(self.row_pair_host).to(self.device)
-        self._out = {}
-        self.out_offsets(None)
-
-    def out_rows(self, target_length=None):
-        """Rows each pair contributes to the fused output: min(n, target_length)."""
-        return self.n if target_length is None else np.minimum(self.n, max(int(target_length), 0))
-
-    def out_offsets(self, target_length=None):
-        """(device int64 [P + 1] row offsets of the fused output, host total) for a target length; uploaded once per
-        length and kept, so that a repeated fusion_batch call moves nothing between host and device."""
-        key = None if target_length is None else max(int(target_length), 0)
-        if key not in self._out:
-            off = np.concatenate([[0], np.cumsum(self.out_rows(key))]).astype(np.int64)
-            self._out[key] = (torch.from_numpy(off).to(self.device), int(off[-1]))
-        return self._out[key]
-
-
 def fusion_batch(tables, v, a, target_length=None, keep_cost=False):
     """Cost matrix, exact DTW path and path-weighted gather (features/fusion.py:7-32) of every pair of ``tables`` in one
     fixed set of launches: one for the cost tiles, one per non-empty size class for the DTW, one for the gather.  ``v``
@@ -1533,19 +1489,11 @@ def fusion_batch(tables, v, a, target_length=None, keep_cost=False):
       total float64 [P]; rowcount int32 [sum n] with row_offsets int64 [P]; cost float64 [sum n*m] (keep_cost only, pair
       p's matrix row-major at tables.cell_off[p]).
     Pair for pair the values are those of cdist / dtw_path / gather_scale.  Nothing synchronises with the host."""
-    if not isinstance(tables, FusionTables):
-        raise ValueError("fusion_batch: tables must be an ops.FusionTables")
-    for t, name in ((v, "v"), (a, "a")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"fusion_batch: {name} must be a device tensor (there is no CPU fallback)")
-        if t.dtype != torch.float32:
-            raise ValueError(f"fusion_batch: {name} must be float32, got {t.dtype}")
-        if t.dim() != 2 or not t.is_contiguous():
-            raise ValueError(f"fusion_batch: {name} must be a contiguous 2-D matrix, got shape {tuple(t.shape)}")
+    _tables_arg(tables, FusionTables, "fusion_batch")
+    _device_arg(v, "v", "fusion_batch", (torch.float32,), ndim=2, device=tables.device)
+    _device_arg(a, "a", "fusion_batch", (torch.float32,), ndim=2, device=tables.device)
     if v.shape[1] != a.shape[1] or v.shape[1] == 0:
         raise ValueError(f"fusion_batch: v and a must have the same number of columns, got {v.shape[1]} and {a.shape[1]}")
-    if tables.device != v.device or a.device != v.device:
-        raise ValueError("fusion_batch: tables, v and a must be on the same device")
     if tables.v_rows_needed > v.shape[0] or tables.a_rows_needed > a.shape[0]:
         raise ValueError(f"fusion_batch: the pairs reach row {tables.v_rows_needed} of v ({v.shape[0]} rows) and row "
                          f"{tables.a_rows_needed} of a ({a.shape[0]} rows)")
@@ -1582,61 +1530,8 @@ def fusion_batch(tables, v, a, target_length=None, keep_cost=False):
 
 
 # --------------------------------------------------------------------------- batched evaluation
-EVAL_MAX_T = 32768       # rows of one video: 4 T^4 < 2^63, so the fold's sums and the host's products fit int64
-EVAL_TILE = 256          # rows of a video per workgroup of the pair-count kernel
-EVAL_CHUNK = 1024        # columns it stages through LDS per step
 EVAL_COLUMNS = ("T", "n_pred", "n_tgt", "tp", "S2", "E_x", "E_y", "S_xy", "S_xx", "S_yy")
 _EVAL_DTYPES = {torch.float32: 4, torch.float64: 8}
-
-
-class EvalTables:
-    """The host plan of one batch layout for eval_counts, built once from the host row offsets [V + 1] of the videos
-    in the concatenated score vectors (video v is rows offsets[v] .. offsets[v + 1]).
-
-    Host side (numpy): ``offsets``, ``lengths``, ``nvideos``, ``rows`` (= offsets[-1], the rows the vectors must have),
-    ``max_t``, ``tiles`` int32 [ntiles, 2] = (video, row tile of 256 rows), ``ntiles``.  Device side: ``offsets_t``
-    int64 [V + 1], ``tiles_t``.  ``device="cpu"`` keeps everything on the host (the builder can be checked without a
-    GPU).  Refused, each with a ValueError: a video shorter than 2 rows (no pair to rank) or longer than 32768,
-    decreasing or negative offsets, 2^31 rows or more."""
-
-    def __init__(self, offsets_host, device=None):
-        off = np.asarray(offsets_host, dtype=np.int64).reshape(-1)
-        if off.size == 0:
-            raise ValueError("eval_counts: offsets must hold V + 1 entries (a single 0 for an empty batch)")
-        if off[0] < 0:
-            raise ValueError("eval_counts: negative row offset")
-        t = np.diff(off)
-        if (t < 0).any():
-            raise ValueError("eval_counts: the offsets decrease")
-        if off[-1] >= 1 << 31:
-            raise ValueError(f"eval_counts: {int(off[-1])} rows, the kernels index rows below 2^31")
-        if (t < 2).any():
-            raise ValueError(f"eval_counts: a video has {int(t.min())} rows; a rank correlation needs at least 2")
-        if (t > EVAL_MAX_T).any():
-            raise ValueError(f"eval_counts: a video has {int(t.max())} rows, above the int64-exact limit {EVAL_MAX_T}")
-        self.offsets, self.lengths, self.nvideos = off, t, int(t.size)
-        self.rows = int(off[-1])
-        self.max_t = int(t.max()) if t.size else 0
-        per = -(-t // EVAL_TILE)
-        self.ntiles = int(per.sum())
-        vid = np.repeat(np.arange(self.nvideos, dtype=np.int64), per)
-        first = np.concatenate([[0], np.cumsum(per)])[:-1].astype(np.int64)
-        k = np.arange(self.ntiles, dtype=np.int64) - np.repeat(first, per)
-        self.tiles = np.stack([vid, k], 1).astype(np.int32).reshape(-1, 2)
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.offsets_t = torch.from_numpy(off).to(torch.device(device))
-        self.device = self.offsets_t.device
-        self.tiles_t = torch.from_numpy(self.tiles).to(self.device)
-
-
-def _eval_vector(t, name, what, dtypes):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{what}: {name} must be a device tensor (there is no CPU fallback)")
-    if t.dtype not in dtypes:
-        raise ValueError(f"{what}: {name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
-    if t.dim() != 1 or not t.is_contiguous():
-        raise ValueError(f"{what}: {name} must be a contiguous vector, got shape {tuple(t.shape)}")
 
 
 def _segment_mean_mask(x, offsets_t, nseg, mask):
@@ -1651,12 +1546,11 @@ def segment_mean_mask(x, offsets):
     device vector ``x``: mean[v] is np.mean(x[a:b]) bit for bit (numpy's reduction order) and mask[r] = x[r] > mean[v]
     - evaluation.metrics.select_frames per segment without a download.  ``offsets``: host sequence or int64 device
     tensor [V + 1], non-decreasing, inside x; rows outside every segment get mask 0; an empty segment's mean is NaN."""
-    _eval_vector(x, "x", "segment_mean_mask", (torch.float32, torch.float64))
+    _device_arg(x, "x", "segment_mean_mask", (torch.float32, torch.float64), ndim=1)
     if isinstance(offsets, torch.Tensor):
-        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1 or not offsets.is_contiguous():
-            raise ValueError("segment_mean_mask: offsets must be a contiguous int64 vector of V + 1 entries")
-        if offsets.device != x.device:
-            raise ValueError("segment_mean_mask: x and offsets must be on the same device")
+        _device_arg(offsets, "offsets", "segment_mean_mask", (torch.int64,), ndim=1, device=x.device)
+        if offsets.numel() < 1:
+            raise ValueError("segment_mean_mask: offsets must hold V + 1 entries")
         off_t = offsets
     else:
         off = np.asarray(offsets, dtype=np.int64).reshape(-1)
@@ -1673,12 +1567,9 @@ def eval_counts(tables, pred, target):
     S_yy).  ``pred`` float32 [R] and ``target`` float32 or float64 [R] are device vectors (values finite); the masks
     are x > np.mean(x) per video with numpy's reduction order in each vector's own dtype.  Nothing synchronises with
     the host; evaluation.metrics.metrics_from_counts finishes the O(V) float work after one download."""
-    if not isinstance(tables, EvalTables):
-        raise ValueError("eval_counts: tables must be an ops.EvalTables")
-    _eval_vector(pred, "pred", "eval_counts", (torch.float32,))
-    _eval_vector(target, "target", "eval_counts", (torch.float32, torch.float64))
-    if tables.device != pred.device or target.device != pred.device:
-        raise ValueError("eval_counts: tables, pred and target must be on the same device")
+    _tables_arg(tables, EvalTables, "eval_counts")
+    _device_arg(pred, "pred", "eval_counts", (torch.float32,), ndim=1, device=tables.device)
+    _device_arg(target, "target", "eval_counts", (torch.float32, torch.float64), ndim=1, device=tables.device)
     rows = pred.shape[0]
     if target.shape[0] != rows or tables.rows > rows:
         raise ValueError(f"eval_counts: the videos reach row {tables.rows}; pred has {rows} rows and target "
@@ -1703,46 +1594,11 @@ def eval_counts(tables, pred, target):
 
 
 # --------------------------------------------------------------------------- batched training
-class SeqTable:
-    """Row offsets of a ragged batch of V videos (video v is rows offsets[v] .. offsets[v + 1] of the concatenated
-    rows), validated on the host and uploaded ONCE: ``offsets`` / ``lengths`` (numpy int64), ``nseq``, ``rows``,
-    ``max_t`` and the device copy ``offsets_t`` int64 [V + 1] that the recurrences, seq_shift_rows and seq_mse read.
-    ``rows``: the row count the offsets must end at (None: wherever they end).  Refused with a ValueError: fewer than
-    one video, offsets that do not start at 0, an empty video (offsets must increase strictly), a last offset other than
-    ``rows``, 2^31 rows or more.  ``device="cpu"`` keeps the table on the host (the builder is checked without a GPU)."""
-
-    def __init__(self, offsets_host, rows=None, device=None):
-        if isinstance(offsets_host, torch.Tensor):
-            if offsets_host.is_cuda:
-                raise ValueError("SeqTable: the offsets are a HOST array (they are validated before the upload)")
-            offsets_host = offsets_host.numpy()
-        off = np.array(offsets_host, dtype=np.int64).reshape(-1)
-        if off.size < 2:
-            raise ValueError("SeqTable: offsets must hold V + 1 entries for V >= 1 videos")
-        if off[0] != 0:
-            raise ValueError(f"SeqTable: offsets must start at 0, got {int(off[0])}")
-        t = np.diff(off)
-        if (t <= 0).any():
-            raise ValueError("SeqTable: an empty video (the offsets must increase strictly)")
-        if rows is not None and off[-1] != rows:
-            raise ValueError(f"SeqTable: the offsets end at {int(off[-1])}, the batch has {int(rows)} rows")
-        if off[-1] >= 1 << 31:
-            raise ValueError(f"SeqTable: {int(off[-1])} rows, the kernels index rows below 2^31")
-        self.offsets, self.lengths, self.nseq = off, t, int(t.size)
-        self.rows, self.max_t = int(off[-1]), int(t.max())
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.offsets_t = torch.from_numpy(off).to(torch.device(device))
-        self.device = self.offsets_t.device
-
-
 def _seq_table(offsets, rows, device, what):
+    """``offsets`` as the SeqTable of ``rows`` rows on ``device``: a prepared table is checked, host offsets are
+    validated and uploaded."""
     if isinstance(offsets, SeqTable):
-        if offsets.rows != rows:
-            raise ValueError(f"{what}: the offsets end at {offsets.rows}, the batch has {rows} rows")
-        if offsets.device != device:
-            raise ValueError(f"{what}: the offsets table is on {offsets.device}, the rows on {device}")
-        return offsets
+        return _tables_arg(offsets, SeqTable, what, device, rows)
     return SeqTable(offsets, rows, device)
 
 
@@ -1751,7 +1607,7 @@ def seq_shift_rows(src, col0, cols, offsets_t, direction, out=None):
     of a recurrence from its outputs (direction +1: forward, the previous row; -1: reverse, the next row).  Exact
     copies.  ``src`` fp32 [R, C] device, unit column stride; ``offsets_t`` int64 [V + 1] device (SeqTable.offsets_t:
     starts at 0, increases, ends at R).  Returns fp32 [R, cols]."""
-    _dev(src, offsets_t)
+    _dev(src)
     _f32(src, "src")
     _rowmajor2d(src, "src")
     rows, width = src.shape
@@ -1759,10 +1615,9 @@ def seq_shift_rows(src, col0, cols, offsets_t, direction, out=None):
         raise ValueError(f"seq_shift_rows: direction must be +1 or -1, got {direction}")
     if col0 < 0 or cols <= 0 or col0 + cols > width:
         raise ValueError(f"seq_shift_rows: columns {col0} .. {col0 + cols} of a matrix {width} wide")
-    if offsets_t.dtype != torch.int64 or offsets_t.dim() != 1 or offsets_t.numel() < 2 or not offsets_t.is_contiguous():
-        raise ValueError("seq_shift_rows: offsets_t must be a contiguous int64 vector of V + 1 entries")
-    if offsets_t.device != src.device:
-        raise ValueError("seq_shift_rows: src and offsets_t must be on the same device")
+    _device_arg(offsets_t, "offsets_t", "seq_shift_rows", (torch.int64,), ndim=1, device=src.device)
+    if offsets_t.numel() < 2:
+        raise ValueError("seq_shift_rows: offsets_t must hold V + 1 entries for V >= 1 videos")
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.float32, device=src.device)
     elif out.dtype != torch.float32 or out.shape != (rows, cols) or not out.is_contiguous():
@@ -1803,10 +1658,8 @@ def seq_mse(scores, targets, offsets):
     per video, what F.mse_loss against the reference's single shot score computes) or [R] (one per row); ``offsets``:
     host array-like [V + 1] or an ops.SeqTable.  The batch loss of a step is ``seq_mse(...).mean()``: its gradient is the
     average of the per-video gradients, what dist.allreduce_gradients gives V ranks that take one video each."""
-    _eval_vector(scores, "scores", "seq_mse", (torch.float32,))
-    _eval_vector(targets, "targets", "seq_mse", (torch.float32,))
-    if targets.device != scores.device:
-        raise ValueError("seq_mse: scores and targets must be on the same device")
+    _device_arg(scores, "scores", "seq_mse", (torch.float32,), ndim=1)
+    _device_arg(targets, "targets", "seq_mse", (torch.float32,), ndim=1, device=scores.device)
     table = _seq_table(offsets, scores.shape[0], scores.device, "seq_mse")
     if targets.shape[0] not in (table.nseq, table.rows):
         raise ValueError(f"seq_mse: targets must hold one entry per video ({table.nseq}) or per row ({table.rows}), got "
@@ -1815,88 +1668,15 @@ def seq_mse(scores, targets, offsets):
 
 
 # --------------------------------------------------------------------------- batched shot detection and sampling
-SHOT_INTERVAL = 3        # features/extractors.py FRAME_INTERVAL: the sampled frames are the multiples of 3,
-SHOT_MAX_FRAMES = 100    # MAX_FRAMES: at most 100 per shot,
-SHOT_MICRO_BATCH = 4     # MICRO_BATCH: in BatchNorm groups of 4 with a shorter tail group
-
-
-class ShotTables:
-    """The host plan of one batch layout for the batched shot detector, built once from the host frame offsets [V + 1]
-    of the videos in the concatenated frames (video v is frames offsets[v] .. offsets[v + 1]) and ``min_scene_len``.
-
-    Host side (numpy): ``offsets``, ``lengths``, ``nvideos``, ``frames`` (= offsets[-1]), ``min_scene_len``, ``cut_off``
-    int64 [V + 1] (video v's slot of the cut buffer: (n_v - 1) // min_scene_len entries, the most the greedy rule can
-    place) and the capacities, all from the offsets alone: ``cut_cap``, ``shot_cap`` = sum of (slot + 1), ``sample_cap``
-    = sum of ceil(n_v / 3) (the shots of a video tile it, so they hold at most its multiples of 3) and ``group_cap`` =
-    sum of (ceil(n_v / 3) // 4 + slot + 1) (sum of ceil(c / 4) <= (F + 3 S) / 4 <= F // 4 + S in integers).  Device side:
-    ``offsets_t``, ``cut_off_t``.  ``device="cpu"`` keeps everything on the host (the builder can be checked without a
-    GPU).  Refused, each with a ValueError: an empty batch, offsets that do not start at 0 or do not increase strictly
-    (an empty video), more than 2^24 frames (the frame is on grid x in workgroups of 256, and a launch holds fewer than
-    2^32 threads per grid dimension), min_scene_len < 1."""
-
-    def __init__(self, offsets_host, min_scene_len=15, device=None):
-        if isinstance(offsets_host, torch.Tensor):
-            if offsets_host.is_cuda:
-                raise ValueError("ShotTables: the offsets are a HOST array (they are validated before the upload)")
-            offsets_host = offsets_host.numpy()
-        off = np.array(offsets_host, dtype=np.int64).reshape(-1)
-        if off.size < 2:
-            raise ValueError("ShotTables: offsets must hold V + 1 entries for V >= 1 videos (the batch is empty)")
-        if off[0] != 0:
-            raise ValueError(f"ShotTables: offsets must start at 0, got {int(off[0])}")
-        n = np.diff(off)
-        if (n <= 0).any():
-            raise ValueError("ShotTables: the offsets must ascend strictly (a video is empty or the offsets decrease)")
-        if off[-1] > 1 << 24:
-            raise ValueError(f"ShotTables: {int(off[-1])} frames, one launch takes at most 2^24")
-        if int(min_scene_len) < 1:
-            raise ValueError(f"ShotTables: min_scene_len must be >= 1, got {min_scene_len}")
-        self.offsets, self.lengths, self.nvideos, self.frames = off, n, int(n.size), int(off[-1])
-        self.min_scene_len = int(min_scene_len)
-        slots = (n - 1) // self.min_scene_len
-        thirds = -(-n // SHOT_INTERVAL)
-        self.cut_off = np.concatenate([[0], np.cumsum(slots)]).astype(np.int64)
-        self.cut_cap = int(slots.sum())
-        self.shot_cap = int((slots + 1).sum())
-        self.sample_cap = int(thirds.sum())
-        self.group_cap = int((thirds // SHOT_MICRO_BATCH + slots + 1).sum())
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.offsets_t = torch.from_numpy(off).to(torch.device(device))
-        self.device = self.offsets_t.device
-        self.cut_off_t = torch.from_numpy(self.cut_off).to(self.device)
-
-
-def _shot_tables_arg(tables, what):
-    if not isinstance(tables, ShotTables):
-        raise ValueError(f"{what}: tables must be an ops.ShotTables")
-    if not tables.device.type == "cuda":
-        raise ValueError(f"{what}: the tables are on the host (there is no CPU fallback)")
-
-
-def _i64_vector(t, name, what, device, numel=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{what}: {name} must be a device tensor (there is no CPU fallback)")
-    if t.dtype != torch.int64 or not t.is_contiguous() or (numel is not None and t.numel() != numel):
-        raise ValueError(f"{what}: {name} must be a contiguous int64 tensor" + (f" of {numel} entries" if numel else ""))
-    if t.device != device:
-        raise ValueError(f"{what}: {name} is on {t.device}, the tables on {device}")
-
-
 def hsv_frame_diff_batch(frames_u8, tables, step=1, raw=False):
     """frames uint8 [N,h,w,3] on device, the videos of ``tables`` concatenated -> int64 [N,3] sums of |dH|,|dS|,|dV|
     against the previous frame of the same video: row for row the integers of one hsv_frame_diff call per video (zeros
     at every video's first frame), in one launch and with N not limited to 65 536.  raw=True returns the int32 [N,3]
     buffer of uint32 bit patterns the kernel wrote (what shot_cuts_batch reads)."""
-    _shot_tables_arg(tables, "hsv_frame_diff_batch")
-    if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda:
-        raise ValueError("hsv_frame_diff_batch: frames must be a device tensor (there is no CPU fallback)")
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
-        raise ValueError("hsv_frame_diff_batch: frames must be contiguous uint8 [n,h,w,3]")
+    _tables_arg(tables, ShotTables, "hsv_frame_diff_batch")
+    _device_arg(frames_u8, "frames", "hsv_frame_diff_batch", (torch.uint8,), shape=(tables.frames, None, None, 3),
+                device=tables.device)
     n, h, w, _ = frames_u8.shape
-    if n != tables.frames or frames_u8.device != tables.device:
-        raise ValueError(f"hsv_frame_diff_batch: {n} frames on {frames_u8.device}, the tables hold {tables.frames} on "
-                         f"{tables.device}")
     if int(step) < 1:
         raise ValueError(f"hsv_frame_diff_batch: step must be >= 1, got {step}")
     sums = torch.empty((n, 3), dtype=torch.int32, device=frames_u8.device)
@@ -1911,14 +1691,8 @@ def shot_cuts_batch(tables, sums, pixels, threshold=27.0):
     (cuts int64 [cut_cap]: video v's cuts, video-relative and ascending, from tables.cut_off[v], the rest of its slot
     not written; totals int64 [V,4] = per video (shots, sampled frames, micro-batch groups, most sampled frames of a shot)), both on the device.  The
     threshold decision is the host's fp64 decision bit for bit; tables.min_scene_len is the greedy rule's gap."""
-    _shot_tables_arg(tables, "shot_cuts_batch")
-    if not isinstance(sums, torch.Tensor) or not sums.is_cuda:
-        raise ValueError("shot_cuts_batch: sums must be a device tensor (there is no CPU fallback)")
-    if sums.dtype != torch.int32 or tuple(sums.shape) != (tables.frames, 3) or not sums.is_contiguous():
-        raise ValueError(f"shot_cuts_batch: sums must be the contiguous int32 [{tables.frames}, 3] buffer of "
-                         "hsv_frame_diff_batch(..., raw=True)")
-    if sums.device != tables.device:
-        raise ValueError("shot_cuts_batch: sums and tables must be on the same device")
+    _tables_arg(tables, ShotTables, "shot_cuts_batch")
+    _device_arg(sums, "sums", "shot_cuts_batch", (torch.int32,), shape=(tables.frames, 3), device=tables.device)
     if not float(pixels) > 0:
         raise ValueError(f"shot_cuts_batch: pixels must be positive, got {pixels}")
     cuts = torch.empty(max(tables.cut_cap, 1), dtype=torch.int64, device=tables.device)
@@ -1938,13 +1712,12 @@ def shot_tables(tables, cuts, totals):
       sample_index int64 [sample_cap] (rows of the concatenated frames); group_offsets int64 [group_cap + 1] (rows of the
       sampled tensor, entry G = F); packed: the int64 buffer all of them but sample_index are views of (ONE download
       brings every table a host needs)."""
-    _shot_tables_arg(tables, "shot_tables")
-    _i64_vector(cuts, "cuts", "shot_tables", tables.device, tables.cut_cap)
-    _i64_vector(totals, "totals", "shot_tables", tables.device, tables.nvideos * 4)
+    _tables_arg(tables, ShotTables, "shot_tables")
+    _device_arg(cuts, "cuts", "shot_tables", (torch.int64,), numel=tables.cut_cap, device=tables.device)
+    _device_arg(totals, "totals", "shot_tables", (torch.int64,), numel=tables.nvideos * 4, device=tables.device)
     nv, dev = tables.nvideos, tables.device
-    sizes = (4, 3 * (nv + 1), 2 * tables.shot_cap, tables.shot_cap + 1, tables.group_cap + 1)
-    packed = torch.empty(sum(sizes), dtype=torch.int64, device=dev)
-    counts, video_off, shots, sample_offsets, group_offsets = torch.split(packed, sizes)
+    packed = torch.empty(sum(tables.packed_sizes), dtype=torch.int64, device=dev)
+    counts, video_off, shots, sample_offsets, group_offsets = torch.split(packed, tables.packed_sizes)
     sample_index = torch.empty(max(tables.sample_cap, 1), dtype=torch.int64, device=dev)
     cuts_arg = cuts if cuts.numel() else torch.empty(1, dtype=torch.int64, device=dev)   # (never read: every slot is empty)
     check(lib().avs_shot_tables_fill(_p(tables.offsets_t), nv, _p(tables.cut_off_t), _p(cuts_arg), _p(totals), _p(video_off),
@@ -1961,17 +1734,11 @@ def gather_rows(src, index, count, out=None):
     element: the row count is read on the device (no download sizes the launch - the grid covers the capacity and the
     surplus workgroups exit).  ``out`` [capacity, ...] (allocated when None); rows from ``count`` on are left as they
     were.  An index outside src is skipped.  capacity < 2^24."""
-    for t, name in ((src, "src"), (index, "index"), (count, "count")) + (((out, "out"),) if out is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"gather_rows: {name} must be a device tensor (there is no CPU fallback)")
-    if src.dim() < 1 or not src.is_contiguous():
+    _device_arg(src, "src", "gather_rows")
+    if src.dim() < 1:
         raise ValueError("gather_rows: src must be a contiguous tensor of rows")
-    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
-        raise ValueError("gather_rows: index must be a contiguous int64 vector")
-    if count.dtype != torch.int64 or count.numel() != 1:
-        raise ValueError("gather_rows: count must be an int64 tensor of one element")
-    if index.device != src.device or count.device != src.device:
-        raise ValueError("gather_rows: src, index and count must be on the same device")
+    _device_arg(index, "index", "gather_rows", (torch.int64,), ndim=1, device=src.device)
+    _device_arg(count, "count", "gather_rows", (torch.int64,), numel=1, device=src.device, contiguous=False)
     cap = index.numel()
     row_shape = tuple(src.shape[1:])
     row_bytes = int(np.prod(row_shape, dtype=np.int64)) * src.element_size()
@@ -1979,9 +1746,8 @@ def gather_rows(src, index, count, out=None):
         raise ValueError(f"gather_rows: rows of shape {row_shape} are empty")
     if out is None:
         out = torch.empty((cap,) + row_shape, dtype=src.dtype, device=src.device)
-    elif out.dtype != src.dtype or tuple(out.shape) != (cap,) + row_shape or not out.is_contiguous() or \
-            out.device != src.device:
-        raise ValueError(f"gather_rows: out must be a contiguous {src.dtype} tensor of shape {(cap,) + row_shape}")
+    else:
+        _device_arg(out, "out", "gather_rows", (src.dtype,), shape=(cap,) + row_shape, device=src.device)
     check(lib().avs_gather_rows_u8(_p(src), src.shape[0], row_bytes, _p(index), _p(count), cap, _p(out), _stream()),
           "avs_gather_rows_u8")
     return out

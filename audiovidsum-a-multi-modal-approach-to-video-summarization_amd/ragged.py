@@ -1,0 +1,225 @@
+"""Host plans of the ragged-batch layers: row offsets validated on the host and uploaded once (RaggedOffsets and the
+three tables built on it - EvalTables, SeqTable, ShotTables) and the pair tables of the batched fusion (FusionTables).
+Pure host code on numpy and torch: nothing here touches the kernel library, so the plans can be built and checked with
+``device="cpu"`` where there is no GPU.  ops.py re-exports every name and holds the launch wrappers that take them."""
+import numpy as np
+import torch
+
+FUSION_MAX_N = 6400      # rows of the visual side of one pair (the per-pair limit of dtw_path)
+FUSION_SMALL_L = 64      # size classes by l = min(n, m): l <= 64 one wave per pair (four pairs per workgroup),
+FUSION_MID_L = 512       # l <= 512 one 256-thread workgroup per pair, above that one 1024-thread workgroup
+_FUSION_TILE = 32        # the cost kernel's output tile
+
+EVAL_MAX_T = 32768       # rows of one video: 4 T^4 < 2^63, so the fold's sums and the host's products fit int64
+EVAL_TILE = 256          # rows of a video per workgroup of the pair-count kernel
+EVAL_CHUNK = 1024        # columns it stages through LDS per step
+
+SHOT_INTERVAL = 3        # features/extractors.py FRAME_INTERVAL: the sampled frames are the multiples of 3,
+SHOT_MAX_FRAMES = 100    # MAX_FRAMES: at most 100 per shot,
+SHOT_MICRO_BATCH = 4     # MICRO_BATCH: in BatchNorm groups of 4 with a shorter tail group
+
+
+def exclusive_offsets(lengths):
+    """int64 [len + 1]: the exclusive prefix sums of ``lengths`` and, last, their total."""
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    out = np.zeros(lengths.size + 1, dtype=np.int64)
+    np.cumsum(lengths, out=out[1:])
+    return out
+
+
+def segment_tiles(per):
+    """Segment p owns per[p] tiles: (segment, k) int64 [sum(per)] each, k counting 0 .. per[segment] - 1."""
+    per = np.asarray(per, dtype=np.int64).reshape(-1)
+    segment = np.repeat(np.arange(per.size, dtype=np.int64), per)
+    k = np.arange(segment.size, dtype=np.int64) - np.repeat(exclusive_offsets(per)[:-1], per)
+    return segment, k
+
+
+def _upload(device, *arrays):
+    """The numpy ``arrays`` as tensors on ``device``: None = the current HIP device, "cpu" = they stay on the host."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    return [torch.from_numpy(a).to(device) for a in arrays]
+
+
+def _bound(n):
+    return f"2^{n.bit_length() - 1}" if n & (n - 1) == 0 else str(n)
+
+
+class RaggedOffsets:
+    """Row offsets [V + 1] of a ragged batch of V segments (segment v is rows offsets[v] .. offsets[v + 1] of the
+    concatenated rows), validated on the host and uploaded ONCE.
+
+    Host side (numpy int64): ``offsets``, ``lengths``; ``count`` (V), ``total`` (= offsets[-1]) and ``max_len`` (0 for
+    an empty batch).  Device side: ``offsets_t`` int64 [V + 1] on ``device`` (None: the current HIP device; "cpu": it
+    stays on the host).  ``what`` starts every message.  The rules, each refused with a ValueError: ``zero_start`` (the
+    first offset is 0, else only non-negative), ``allow_empty`` (a lone [0] for V = 0), ``min_length`` / ``max_length``
+    of a segment, ``max_total`` for the last offset (``total_inclusive``: it may be reached) and ``rows`` (what the last
+    offset must equal; None: wherever the offsets end).  Decreasing offsets and a device tensor are always refused:
+    the offsets are a host array."""
+
+    def __init__(self, offsets_host, what, *, device=None, zero_start=True, allow_empty=False, min_length=1,
+                 max_length=None, max_total=1 << 31, total_inclusive=False, rows=None):
+        if isinstance(offsets_host, torch.Tensor):
+            if offsets_host.is_cuda:
+                raise ValueError(f"{what}: the offsets are a HOST array (they are validated before the upload)")
+            offsets_host = offsets_host.numpy()
+        off = np.array(offsets_host, dtype=np.int64).reshape(-1)
+        if off.size < (1 if allow_empty else 2):
+            raise ValueError(f"{what}: offsets must hold V + 1 entries" + (" (a single 0 for an empty batch)"
+                             if allow_empty else " for V >= 1 videos (the batch is empty)"))
+        if off[0] < 0:
+            raise ValueError(f"{what}: negative row offset")
+        if zero_start and off[0] != 0:
+            raise ValueError(f"{what}: offsets must start at 0, got {int(off[0])}")
+        t = np.diff(off)
+        shortest, longest = (int(t.min()), int(t.max())) if t.size else (min_length, 0)
+        if shortest < 0:
+            raise ValueError(f"{what}: the offsets decrease")
+        total = int(off[-1])
+        if rows is not None and total != rows:
+            raise ValueError(f"{what}: the offsets end at {total}, the batch has {int(rows)} rows")
+        if total > max_total or (total == max_total and not total_inclusive):
+            raise ValueError(f"{what}: {total} rows, the kernels take {'at most' if total_inclusive else 'fewer than'} "
+                             f"{_bound(max_total)}")
+        if shortest < min_length:
+            raise ValueError(f"{what}: a video has {shortest} rows, it needs at least {min_length} (the offsets "
+                             "must increase)")
+        if max_length is not None and longest > max_length:
+            raise ValueError(f"{what}: a video has {longest} rows, above the limit {max_length}")
+        self.offsets, self.lengths, self.count, self.total, self.max_len = off, t, int(t.size), total, longest
+        self.offsets_t, = _upload(device, off)
+        self.device = self.offsets_t.device
+
+
+class EvalTables(RaggedOffsets):
+    """The host plan of one batch layout for eval_counts, built once from the host row offsets [V + 1] of the videos
+    in the concatenated score vectors (video v is rows offsets[v] .. offsets[v + 1]).
+
+    Host side (numpy): ``offsets``, ``lengths``, ``nvideos``, ``rows`` (= offsets[-1], the rows the vectors must have),
+    ``max_t``, ``tiles`` int32 [ntiles, 2] = (video, row tile of 256 rows), ``ntiles``.  Device side: ``offsets_t``
+    int64 [V + 1], ``tiles_t``.  ``device="cpu"`` keeps everything on the host (the builder can be checked without a
+    GPU).  Refused, each with a ValueError: a video shorter than 2 rows (no pair to rank) or longer than 32768 (the
+    int64-exact limit), decreasing or negative offsets, 2^31 rows or more.  The first video may start after row 0 and
+    the batch may be empty ([0])."""
+
+    def __init__(self, offsets_host, device=None):
+        super().__init__(offsets_host, "eval_counts", device=device, zero_start=False, allow_empty=True, min_length=2,
+                         max_length=EVAL_MAX_T)
+        self.nvideos, self.rows, self.max_t = self.count, self.total, self.max_len
+        self.tiles = np.stack(segment_tiles(-(-self.lengths // EVAL_TILE)), 1).astype(np.int32).reshape(-1, 2)
+        self.ntiles = self.tiles.shape[0]
+        self.tiles_t, = _upload(self.device, self.tiles)
+
+
+class SeqTable(RaggedOffsets):
+    """Row offsets of a ragged batch of V videos for the batched training step: ``offsets`` / ``lengths`` (numpy
+    int64), ``nseq``, ``rows``, ``max_t`` and the device copy ``offsets_t`` int64 [V + 1] that the recurrences,
+    seq_shift_rows and seq_mse read.  ``rows``: the row count the offsets must end at (None: wherever they end).
+    Refused with a ValueError: fewer than one video, offsets that do not start at 0, an empty video (offsets must
+    increase strictly), a last offset other than ``rows``, 2^31 rows or more.  ``device="cpu"`` keeps the table on the
+    host (the builder is checked without a GPU)."""
+
+    def __init__(self, offsets_host, rows=None, device=None):
+        super().__init__(offsets_host, "SeqTable", device=device, rows=rows)
+        self.nseq, self.rows, self.max_t = self.count, self.total, self.max_len
+
+
+class ShotTables(RaggedOffsets):
+    """The host plan of one batch layout for the batched shot detector, built once from the host frame offsets [V + 1]
+    of the videos in the concatenated frames (video v is frames offsets[v] .. offsets[v + 1]) and ``min_scene_len``.
+
+    Host side (numpy): ``offsets``, ``lengths``, ``nvideos``, ``frames`` (= offsets[-1]), ``min_scene_len``, ``cut_off``
+    int64 [V + 1] (video v's slot of the cut buffer: (n_v - 1) // min_scene_len entries, the most the greedy rule can
+    place) and the capacities, all from the offsets alone: ``cut_cap``, ``shot_cap`` = sum of (slot + 1), ``sample_cap``
+    = sum of ceil(n_v / 3) (the shots of a video tile it, so they hold at most its multiples of 3) and ``group_cap`` =
+    sum of (ceil(n_v / 3) // 4 + slot + 1) (sum of ceil(c / 4) <= (F + 3 S) / 4 <= F // 4 + S in integers);
+    ``packed_sizes``: the entries of the five parts of ops.shot_tables' one int64 buffer - counts, per-video offsets,
+    shots, sample offsets, group offsets - at those capacities.  Device side: ``offsets_t``, ``cut_off_t``.
+    ``device="cpu"`` keeps everything on the host (the builder can be checked without a GPU).  Refused, each with a
+    ValueError: an empty batch, offsets that do not start at 0 or do not increase strictly (an empty video), more than
+    2^24 frames (the frame is on grid x in workgroups of 256, and a launch holds fewer than 2^32 threads per grid
+    dimension), min_scene_len < 1."""
+
+    def __init__(self, offsets_host, min_scene_len=15, device=None):
+        super().__init__(offsets_host, "ShotTables", device=device, max_total=1 << 24, total_inclusive=True)
+        if int(min_scene_len) < 1:
+            raise ValueError(f"ShotTables: min_scene_len must be >= 1, got {min_scene_len}")
+        self.nvideos, self.frames, self.min_scene_len = self.count, self.total, int(min_scene_len)
+        slots = (self.lengths - 1) // self.min_scene_len
+        thirds = -(-self.lengths // SHOT_INTERVAL)
+        self.cut_off = exclusive_offsets(slots)
+        self.cut_cap = int(slots.sum())
+        self.shot_cap = int((slots + 1).sum())
+        self.sample_cap = int(thirds.sum())
+        self.group_cap = int((thirds // SHOT_MICRO_BATCH + slots + 1).sum())
+        self.packed_sizes = (4, 3 * (self.nvideos + 1), 2 * self.shot_cap, self.shot_cap + 1, self.group_cap + 1)
+        self.cut_off_t, = _upload(self.device, self.cut_off)
+
+
+class FusionTables:
+    """The host plan of one batch layout for fusion_batch, built once from the host list of pairs
+    ``(v_row0, n, a_row0, m)``: pair p is rows v_row0 .. v_row0 + n of the visual matrix against rows a_row0 ..
+    a_row0 + m of the audio matrix.  Nothing is padded; the pairs may leave gaps and come in any order.
+
+    Host side (numpy): ``n``, ``m``, ``cell_off`` (first element of the pair's [n, m] block in the cost buffer and the
+    code workspace), ``path_off`` / ``path_cap`` (its path slot: n + m - 1 rows), ``row_off`` (first of its n row
+    counts), ``cls`` (size class 0/1/2), ``order`` (pairs sorted by class, longest sweep first inside a class),
+    ``class_count``, ``class_max_l``, ``tiles`` (pair, row tile, column tile), ``cells``, ``path_rows``, ``rows``,
+    ``workspace_bytes``.  Device side: ``pairs`` int64 [P, 8], ``order_t``, ``tiles_t``, ``row_pair`` int32 [rows].
+    ``device="cpu"`` keeps everything on the host (the table builder can be checked without a GPU)."""
+
+    def __init__(self, pairs, device=None):
+        arr = np.asarray(list(pairs), dtype=np.int64).reshape(-1, 4)
+        v0, n, a0, m = (arr[:, k].copy() for k in range(4))
+        if (n <= 0).any() or (m <= 0).any():
+            raise ValueError("fusion_batch: a pair is empty (n == 0 or m == 0)")
+        if (v0 < 0).any() or (a0 < 0).any():
+            raise ValueError("fusion_batch: negative row offset")
+        if (n > FUSION_MAX_N).any():
+            raise ValueError(f"fusion_batch: a pair has n = {int(n.max())} rows, above the LDS-resident limit {FUSION_MAX_N}")
+        if (m >= 1 << 30).any():
+            raise ValueError("fusion_batch: a pair has m >= 2^30 rows")
+        npairs = arr.shape[0]
+        self.npairs, self.v_row0, self.n, self.a_row0, self.m = npairs, v0, n, a0, m
+        self.v_rows_needed = int((v0 + n).max()) if npairs else 0
+        self.a_rows_needed = int((a0 + m).max()) if npairs else 0
+        cell, path, row = exclusive_offsets(n * m), exclusive_offsets(n + m - 1), exclusive_offsets(n)
+        self.cell_off, self.path_off, self.row_off = cell[:-1], path[:-1], row[:-1]
+        self.path_cap = n + m - 1
+        self.cells, self.path_rows, self.rows = int(cell[-1]), int(path[-1]), int(row[-1])
+        small = np.minimum(n, m)
+        self.cls = (small > FUSION_SMALL_L).astype(np.int64) + (small > FUSION_MID_L)
+        # by class, then the most anti-diagonals first (neighbours in a class-0 workgroup sweep about as long); stable
+        self.order = np.lexsort((np.arange(npairs), -(n + m), self.cls)).astype(np.int32)
+        self.class_count = [int((self.cls == c).sum()) for c in range(3)]
+        self.class_max_l = [int(small[self.cls == c].max()) if self.class_count[c] else 0 for c in range(3)]
+        self.max_n = int(n.max()) if npairs else 0
+        ti, tj = -(-n // _FUSION_TILE), -(-m // _FUSION_TILE)
+        tp, k = segment_tiles(ti * tj)
+        self.ntiles = tp.size
+        self.tiles = np.stack([tp, k // tj[tp], k % tj[tp]], 1).astype(np.int32).reshape(-1, 3)
+        self.row_pair_host = np.repeat(np.arange(npairs, dtype=np.int32), n)
+        self.workspace_bytes = (self.cells + 255) & ~255     # avs_dtw_batch_workspace_bytes: one code byte per cell
+        table = np.zeros((npairs, 8), dtype=np.int64)
+        for col, x in enumerate((v0, n, a0, m, self.cell_off, self.path_off, self.row_off)):
+            table[:, col] = x
+        self.pairs, self.order_t, self.tiles_t, self.row_pair = _upload(device, table, self.order, self.tiles,
+                                                                        self.row_pair_host)
+        self.device = self.pairs.device
+        self._out = {}
+        self.out_offsets(None)
+
+    def out_rows(self, target_length=None):
+        """Rows each pair contributes to the fused output: min(n, target_length)."""
+        return self.n if target_length is None else np.minimum(self.n, max(int(target_length), 0))
+
+    def out_offsets(self, target_length=None):
+        """(device int64 [P + 1] row offsets of the fused output, host total) for a target length; uploaded once per
+        length and kept, so that a repeated fusion_batch call moves nothing between host and device."""
+        key = None if target_length is None else max(int(target_length), 0)
+        if key not in self._out:
+            off = exclusive_offsets(self.out_rows(key))
+            self._out[key] = (_upload(self.device, off)[0], int(off[-1]))
+        return self._out[key]

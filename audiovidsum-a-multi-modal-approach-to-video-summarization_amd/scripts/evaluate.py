@@ -2,10 +2,10 @@
 video per call, B = 1, on the MI355X), then the per-video mean-threshold F1 and rank correlations, averaged.
 Same signature and return keys as the reference; the metric arithmetic lives in evaluation.metrics.
 evaluate_batch is the same evaluation as one ragged batch: one score_rows call, the metrics on the device, one download."""
-import numpy as np
 import torch
 
 from ..evaluation.metrics import summarize_scores, summarize_scores_device
+from ..ragged import exclusive_offsets
 
 
 def predict_dataset(model, dataset):
@@ -44,7 +44,7 @@ def evaluate_batch(model, dataset):
         lengths.append(visual.shape[0])
     if not items:
         raise ValueError("evaluate_batch: empty dataset")
-    offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    offsets = exclusive_offsets(lengths)
     dev = torch.device("cuda", torch.cuda.current_device())
     from .. import ops
     tables = ops.EvalTables(offsets, dev)

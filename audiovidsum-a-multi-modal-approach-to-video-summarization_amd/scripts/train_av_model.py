@@ -18,6 +18,7 @@ from torch.utils.data import DataLoader
 
 from .. import dist as avd, ops
 from ..models.av_model import AVBiLSTMModel
+from ..ragged import exclusive_offsets
 from ..utils.alignments import align_shots_to_annotations
 
 
@@ -61,9 +62,7 @@ def collate_videos(items):
         aud.append(a.float())
         lengths.append(v.shape[0])
         targets.append(shot_scores.float().reshape(1))
-    offsets = torch.zeros(len(items) + 1, dtype=torch.int64)
-    offsets[1:] = torch.cumsum(torch.tensor(lengths, dtype=torch.int64), 0)
-    return torch.cat(vis), torch.cat(aud), offsets, torch.cat(targets)
+    return torch.cat(vis), torch.cat(aud), torch.from_numpy(exclusive_offsets(lengths)), torch.cat(targets)
 
 
 def train_step_batch(model, optimizer, items, device="cuda"):
