@@ -8,6 +8,9 @@ Restates, op by op on torch CPU tensors (fp32), what the reference executes:
   * av_bilstm_forward      models/av_model.py:33-46   (AVBiLSTMModel.forward)
   * lstm_direction         nn.LSTM as used at models/av_model.py:18-23,39-40
                            (gate order i,f,g,o; h0=c0=0)
+  * lstm_recurrence        the recurrence of lstm_direction on the projected input, in
+                           any dtype, returning h, the gates and the cell state: in
+                           float64 the reference of the recurrence kernels
   * mha_seq_first          nn.MultiheadAttention(1024,4) fed [B,T,E] WITHOUT
                            batch_first, models/av_model.py:26,44:
                            softmax over the B axis, per time-step and head
@@ -47,6 +50,33 @@ def lstm_direction(x, w_ih, w_hh, b_ih, b_hh, reverse=False):
         h = o * torch.tanh(c)
         outs[t] = h
     return torch.stack(outs) if t_len else torch.zeros((0, hid), dtype=x.dtype)
+
+
+def lstm_recurrence(xproj, w_hh, reverse=False):
+    """The recurrence of lstm_direction alone, in the dtype of its arguments (float64: the reference of the recurrence
+    kernels, tests/test_gpu_lstm_f64.py).  xproj [T, 4H] is the projected input x @ W_ih^T + b_ih + b_hh, w_hh [4H, H].
+    Returns (h [T, H], gates [T, 4H] post-activation in the order i, f, g, o, cell [T, H]), rows in time order whichever
+    way the sequence is walked; the state starts at zero.  Differentiable torch ops only: torch.autograd.grad of h for a
+    given dL/dh gives dL/dxproj.  Pinned to torch.nn.LSTM in float64 by tests/test_lstm_f64_host.py."""
+    t_len = xproj.shape[0]
+    hid = w_hh.shape[1]
+    h = xproj.new_zeros(hid)
+    c = xproj.new_zeros(hid)
+    hs, gs, cs = [None] * t_len, [None] * t_len, [None] * t_len
+    order = range(t_len - 1, -1, -1) if reverse else range(t_len)
+    xs = xproj.unbind(0)      # (one backward node for all rows: xproj[t] would build a [T, 4H] gradient per step)
+    for t in order:
+        g = xs[t] + w_hh @ h
+        i = torch.sigmoid(g[0:hid])
+        f = torch.sigmoid(g[hid:2 * hid])
+        gg = torch.tanh(g[2 * hid:3 * hid])
+        o = torch.sigmoid(g[3 * hid:4 * hid])
+        c = f * c + i * gg
+        h = o * torch.tanh(c)
+        hs[t], gs[t], cs[t] = h, torch.cat([i, f, gg, o]), c
+    if not t_len:
+        return xproj.new_zeros((0, hid)), xproj.new_zeros((0, 4 * hid)), xproj.new_zeros((0, hid))
+    return torch.stack(hs), torch.stack(gs), torch.stack(cs)
 
 
 def bilstm(x, sd, prefix):
