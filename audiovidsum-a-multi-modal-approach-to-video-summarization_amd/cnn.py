@@ -121,7 +121,8 @@ class Step(NamedTuple):
            step's residual add)
     block  bottleneck index (-1: the stem)
     geom   (convolution geometry, input strides, weight row stride) as the avs_conv2d_nhwc* descriptor takes them
-    cluster  the clustered form: tiles per group"""
+    cluster  the clustered form: tiles per group
+    packed   the clustered form runs packed: tiles of 224 consecutive rows instead of one 196-row tile per map (quarter)"""
     name: str
     form: str
     inp: str = "finished"
@@ -130,6 +131,7 @@ class Step(NamedTuple):
     block: int = -1
     geom: tuple = None
     cluster: int = 1
+    packed: bool = False
 
 
 class ResNet50Runner:
@@ -140,7 +142,8 @@ class ResNet50Runner:
       local      bf16 / f16x2, equal-sized groups of <= 256 rows (14x14 / 7x7 maps): convolution + whole BatchNorm
                  (+ residual + ReLU) in ONE launch, statistics inside a tile (avs_conv2d_nhwc_bnlocal) - nothing raw in HBM;
       cluster    f16x2: the same with a group spread over several tiles that exchange their statistics
-                 (avs_conv2d_nhwc_bncluster);
+                 (avs_conv2d_nhwc_bncluster; pack_groups: on tiles of 224 consecutive rows where the library takes the groups
+                 packed - Step.packed);
       gram       bf16 / f16x2 expanding 1x1 layers with 64 / 128 input channels (conv3 / downsample of layers 1-2):
                  statistics from the input's Gram matrix, then ONE streaming pass with the affine in the epilogue;
       gram_pair  layer 1's first conv1 and downsample read the same input: one Gram matrix, one streaming pass each;
@@ -168,6 +171,8 @@ class ResNet50Runner:
         self.fuse_min_rows, self.fuse_ratio_num, self.fuse_ratio_den = 128, 2, 1   # cout / cin >= num / den (f16x2: >= 2)
         self.bn_local = True         # the one-launch tile-local form where the library takes the shape
         self.bn_cluster = True       # AVS_F16X2: groups of several 14x14 maps in ONE launch (tiles exchange their statistics)
+        self.pack_groups = True      # ... on tiles of 224 consecutive rows where the library takes the groups packed (4-frame
+                                     # groups of 14x14 maps: 7 full tiles per 2 groups instead of 8 of 196 rows)
         self.fused_stem = True       # uint8 frames -> conv1 -> pooled raw map + partial sums in one kernel
         self.stem_raw = True         # bf16: bn1 + ReLU ride in the staging of layer 1's first conv1 / downsample (both take the
                                      # one-pass form on ONE Gram matrix of the stem output): no finishing pass
@@ -252,14 +257,15 @@ class ResNet50Runner:
                 and cout * self.fuse_ratio_den >= cin * self.fuse_ratio_num)
 
     def _tile_local(self, geom, gsz, cluster):
-        """1 = the tile-local form takes the layer, k > 1 = the clustered form with groups of k tiles, 0 = neither."""
+        """(k, packed): k = 1: the tile-local form takes the layer, k > 1: the clustered form with groups of k tiles (packed:
+        in its packed form), 0: neither."""
         g, xs, wrs = geom
         cin, kh, ho, wo, cout = g[3], g[4], g[10], g[11], g[12]
         rows = gsz * ho * wo
         if rows <= 256:
-            return int(ops.conv_bnlocal_tile_rows(self.code, *g, *xs, wrs, cout, rows) is not None)
+            return int(ops.conv_bnlocal_tile_rows(self.code, *g, *xs, wrs, cout, rows) is not None), False
         if not (self.h2 and cluster):
-            return 0
+            return 0, False
         # a group larger than a tile: the map splits into k tiles of 193..224 rows (14 x 14: k = 1, layer 3 with the
         # reference's 4-frame micro-batches; 28 x 28: k = 4) and the group into gsz * k <= 16 of them
         for k in (1, 2, 4, 8, 16):
@@ -269,8 +275,12 @@ class ResNet50Runner:
             if k > 1 and not (kh == 1 and cin >= 512 and cout >= 256):
                 continue
             if (ho * wo) % k == 0 and 192 < (ho * wo) // k <= 224 and 2 <= gsz * k <= 16:
-                return gsz * k if ops.conv_bncluster_ok(self.code, *g, *xs, wrs, cout, rows, gsz * k) else 0
-        return 0
+                # the packed form first (groups of several frames; measured at 4-frame groups only); a shape it declines
+                # keeps the unpacked answer
+                if self.pack_groups and gsz > 1 and ops.conv_bncluster_ok(self.code, *g, *xs, wrs, cout, rows, gsz * k, packed=True):
+                    return gsz * k, True
+                return (gsz * k if ops.conv_bncluster_ok(self.code, *g, *xs, wrs, cout, rows, gsz * k) else 0), False
+        return 0, False
 
     def plan(self, n, group_frames=None, bn_cluster=None):
         """The trunk's steps (Step) in launch order for n frames in BatchNorm groups `group_frames` (forward's
@@ -280,7 +290,7 @@ class ResNet50Runner:
         return self._plan(n, gsz, uniform, self.bn_cluster if bn_cluster is None else bn_cluster)
 
     def _plan(self, n, gsz, uniform, cluster):
-        key = (n, gsz, uniform, bool(cluster), self.bn_local, self.fused_stem, self.stem_raw, self.fuse_conv_bn,
+        key = (n, gsz, uniform, bool(cluster), bool(self.pack_groups), self.bn_local, self.fused_stem, self.stem_raw, self.fuse_conv_bn,
                self.fuse_min_rows, self.fuse_ratio_num, self.fuse_ratio_den, self.defer_bn_apply, self.defer_res_apply,
                self.fold_input_bn, tuple(self.p8_blocks), self.block_hook is None)
         steps = self._plans.get(key)
@@ -294,19 +304,19 @@ class ResNet50Runner:
         local = self.bn_local and fast and (bf16 or h2)
 
         def form(geom, x_p8=False):
-            """(form, cluster) of one convolution + BatchNorm on its own."""
+            """(form, cluster, packed) of one convolution + BatchNorm on its own."""
             g, xs, wrs = geom
             cin, kh, sh, ho, wo, cout = g[3], g[4], g[6], g[10], g[11], g[12]
             if not batch:
-                return "folded", 1
-            k = self._tile_local(geom, gsz, cluster) if local else 0
+                return "folded", 1, False
+            k, packed = self._tile_local(geom, gsz, cluster) if local else (0, False)
             if k:
-                return ("local", 1) if k == 1 else ("cluster", k)
+                return ("local", 1, False) if k == 1 else ("cluster", k, packed)
             if fast and self._gram_ok(cin, cout, kh, sh, gsz * ho * wo):
-                return "gram", 1
+                return "gram", 1, False
             if fast and ops.conv_bnstats_ok(self.code, *g, *xs, wrs, cout, gsz * ho * wo, x_p8=x_p8):
-                return "stats", 1
-            return "split", 1
+                return "stats", 1, False
+            return "split", 1, False
 
         split_forms, tiled = ("stats", "split"), ("local", "cluster")
         pair = self._pair_ok()
@@ -322,8 +332,8 @@ class ResNet50Runner:
             steps = [Step("conv1", "stem_f16x2", out="deferred")]
         else:
             geom = self._stem_geom(n)
-            f, k = form(geom)
-            steps = [Step("conv1", f, geom=geom, cluster=k)]
+            f, k, pk = form(geom)
+            steps = [Step("conv1", f, geom=geom, cluster=k, packed=pk)]
         blocks = list(self._blocks())
         h, cin, x_out = 56, 64, "finished"
         for bi, (name, blk) in enumerate(blocks):
@@ -355,14 +365,14 @@ class ResNet50Runner:
                 steps.append(Step(name + ".conv1+downsample", "gram_pair", "raw" if x_raw else "finished", block=bi, geom=g1))
             else:
                 steps.append(Step(name + ".conv1", f1[0], out="deferred" if fold1 else "finished", block=bi, geom=g1,
-                                  cluster=f1[1]))
+                                  cluster=f1[1], packed=f1[2]))
             steps.append(Step(name + ".conv2", f2[0], "raw" if fold1 else "finished", "deferred" if defer2 else "finished",
-                              block=bi, geom=g2, cluster=f2[1]))
+                              block=bi, geom=g2, cluster=f2[1], packed=f2[2]))
             if gd is not None and not use_pair:
                 steps.append(Step(name + ".downsample", fd[0], out="deferred" if deferd else "finished", block=bi, geom=gd,
-                                  cluster=fd[1]))
+                                  cluster=fd[1], packed=fd[2]))
             steps.append(Step(name + ".conv3", f3[0], "raw" if defer2 else "finished", "p8" if p8 else "finished",
-                              "deferred" if deferd else "downsample" if gd is not None else "identity", bi, g3, f3[1]))
+                              "deferred" if deferd else "downsample" if gd is not None else "identity", bi, g3, f3[1], f3[2]))
             h, cin, x_out, x_raw = hout, planes * 4, steps[-1].out, False
         if len(self._plans) > 64:
             self._plans.clear()
@@ -417,7 +427,7 @@ class ResNet50Runner:
                                   algo_in_elems=x.numel() if stem else None, w_layout=layout, **kw)
 
         if st.form in ("local", "cluster"):
-            conv(act=act, bnlocal=(gmax, gamma, beta, eps, residual), cluster=st.cluster)
+            conv(act=act, bnlocal=(gmax, gamma, beta, eps, residual), cluster=st.cluster, packed=st.packed)
             return (ops.pool2d(y, "max", 3, 2, 1, pooled(), code=self.ecode) if stem else y), None
         affine = None
         if st.form == "folded":

@@ -2090,7 +2090,7 @@ static int conv_geometry(const avs_conv_desc* d, bool has_bias, IgemmParams& p, 
   AVS_REQUIRE(d->w_layout == AVS_W_ROWS || d->w_layout == AVS_W_KSTEP32, AVS_E_ARG, "%s: bad w_layout %d", who,
               d->w_layout);
   p.w_kstep = d->w_layout == AVS_W_KSTEP32 ? 1 : 0;
-  AVS_REQUIRE((d->variant & ~7) == 0, AVS_E_ARG, "%s: bad variant %d", who, d->variant);
+  AVS_REQUIRE((d->variant & ~15) == 0, AVS_E_ARG, "%s: bad variant %d", who, d->variant);
   p.variant = d->variant;
   AVS_REQUIRE((d->formats & ~(AVS_X_F16P8 | AVS_Y_F16P8 | AVS_RES_F16P8)) == 0, AVS_E_ARG, "%s: bad formats %d", who, d->formats);
   AVS_REQUIRE(d->formats == 0 || d->dtype == AVS_F16X2, AVS_E_UNSUPPORTED, "%s: AVS_F16P8 operands belong to the AVS_F16X2 forms", who);
@@ -2327,7 +2327,23 @@ static int bncluster_plan(const avs_conv_desc* d, int64_t rpg, int cluster, Igem
   p.tile_rows = (int)(rpg / cluster);
   p.rows_per_group = (int)rpg;
   p.cluster = cluster;
+  if (d->variant & AVS_CLUSTER_PACKED) {
+    // the packed form: tiles of 224 consecutive rows.  Groups of a multiple of 112 rows put a boundary inside a tile at row
+    // 112 only (an odd multiple: every second group starts there, two groups = rpg / 112 whole tiles; an even one: never)
+    const int64_t per_group = (rpg + 223) / 224;   // tiles a group touches, whether it starts at row 0 or 112 of its first
+    AVS_REQUIRE(rpg >= 224 && (rpg % 224 == 0 || rpg % 224 == 112) && per_group <= 16, AVS_E_UNSUPPORTED,
+                "%s: AVS_CLUSTER_PACKED needs groups of a multiple of 112 rows, at least 224, that touch at most 16 tiles", who);
+    p.tile_rows = 224;
+    p.packed = (int)(rpg % 224 ? rpg / 112 : rpg / 224);
+  }
   return AVS_OK;
+}
+
+// the exchange buffer: a 64-byte header (the error counter) + 8-byte granules [tiles_m][tiles_n][4 waves][64 lanes]; the
+// packed form: [tiles_m][tiles_n][4 waves][2 segments][64 lanes] over its tiles of 224 rows (the last one may be short)
+static int64_t bncluster_workspace(const IgemmParams& p) {
+  if (p.packed) return 64 + (int64_t)((p.M + 223) / 224) * p.tiles_n * 4 * 2 * 64 * 8;
+  return 64 + (int64_t)(p.M / p.tile_rows) * p.tiles_n * 4 * 64 * 8;
 }
 
 extern "C" int64_t avs_conv2d_bncluster_workspace_bytes(const avs_conv_desc* d, int64_t rows_per_group, int cluster) {
@@ -2335,8 +2351,7 @@ extern "C" int64_t avs_conv2d_bncluster_workspace_bytes(const avs_conv_desc* d, 
   const int st = bncluster_plan(d, rows_per_group, cluster, p, "avs_conv2d_bncluster_workspace_bytes");
   if (st != AVS_OK) return st;
   if (p.M == 0) return 64;
-  // a 64-byte header (the error counter) + 8-byte granules [tiles_m][tiles_n][4 waves][64 lanes]
-  return 64 + (int64_t)(p.M / p.tile_rows) * p.tiles_n * 4 * 64 * 8;
+  return bncluster_workspace(p);
 }
 
 extern "C" int avs_conv2d_nhwc_bncluster(const avs_conv_desc* d, const void* d_x, const void* d_w, void* d_y,
@@ -2354,7 +2369,7 @@ extern "C" int avs_conv2d_nhwc_bncluster(const avs_conv_desc* d, const void* d_x
               "%s: y must be 32-byte, the exchange buffer 64-byte aligned", who);
   AVS_REQUIRE(!d_residual || ((((uintptr_t)d_residual) & 31u) == 0 && ldr % 8 == 0 && ldr >= p.N), AVS_E_ALIGN,
               "%s: an AVS_F16X2 residual must be 32-byte aligned with a row stride in multiples of 8 slots, at least cout long", who);
-  const int64_t need = 64 + (int64_t)(p.M / p.tile_rows) * p.tiles_n * 4 * 64 * 8;
+  const int64_t need = bncluster_workspace(p);
   AVS_REQUIRE(xchg_bytes >= need, AVS_E_WORKSPACE, "%s: exchange buffer %lld < %lld bytes", who, (long long)xchg_bytes,
               (long long)need);
   conv_operands(p, d_x, d_w, nullptr, d_y);

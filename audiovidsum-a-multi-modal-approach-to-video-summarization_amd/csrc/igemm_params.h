@@ -60,6 +60,11 @@ struct IgemmParams {
   unsigned epoch;
   unsigned long long* xchg;
   unsigned* xerr;    // a counter of waves whose bounded wait ran out (0 = every exchange completed)
+  // packed form of the clustered BatchNorm (AVS_CLUSTER_PACKED): tiles are 224 consecutive rows of the launch whatever
+  // rows_per_group is (a multiple of 112); a tile meets at most two groups, the boundary inside it at row 112; xchg holds
+  // two granules per lane, [tiles_m][tiles_n][4 waves][2 segments][64].  packed = row tiles per dispatch unit (the tiles
+  // that can wait for each other: those of one group, or of two groups that share a tile), 0 = the unpacked form
+  int packed;
   // input affine of the nine-tap convolution + statistics form (AVS_F16X2, avs_conv2d_nhwc_bnstats_xin): the input is a
   // RAW activation whose BatchNorm (+ ReLU) is applied as each 16-channel block lands in LDS - x = act(x * in_scale[g] +
   // in_shift[g]), g = row / rows_per_group, in_scale / in_shift [groups, cin]

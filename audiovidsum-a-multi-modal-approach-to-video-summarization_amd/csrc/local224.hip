@@ -16,6 +16,10 @@
 // igemm_kernel<..., PIPE, FASTK, SPLIT = 2>: the convolution itself is bit-identical to the 256-row form, the statistics
 // are summed in a different (fixed) order.  Waves 0 and 1 issue six DMA instructions per step, waves 2 and 3 five (352 rows
 // = 5.5 passes of the 256 threads); each wave waits on its own count.
+//
+// Groups larger than a tile run clustered (p.cluster > 1: one tile per 193..224-row member of the group, the tiles exchange
+// their statistics), or PACKED (p.packed: tiles of 224 consecutive rows whatever the group size - a multiple of 112 rows - so
+// no tile runs a 32-row block for 4 live rows; a tile then holds rows of one or of two groups, the boundary at its row 112).
 #include "avs_internal.h"
 #include "igemm_params.h"
 #include <type_traits>
@@ -53,7 +57,26 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
   const unsigned wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
   int tn = wg % p.tiles_n;
   int tm = wg / p.tiles_n;
-  if (p.cluster > 1) {
+  if (p.packed) {
+    // packed clustered form: the tiles that wait for each other are the p.packed row tiles of a unit (one group, or two groups
+    // around a shared tile) - CONSECUTIVE block ids, as below.  Super-unit = 56 row tiles (7- and 14-tile units divide it) x
+    // all column tiles, block = column tile * 56 + row tile: a row tile's column tiles sit on XCD (row tile % 8)
+    const unsigned u_t = (unsigned)p.packed, tnn = (unsigned)p.tiles_n;
+    const unsigned tiles_m = nwg / tnn;
+    const unsigned full = (56u % u_t == 0u) ? (tiles_m / 56u) * 56u : 0u;
+    if (orig < full * tnn) {
+      const unsigned su = orig / (56u * tnn), l = orig - su * (56u * tnn);
+      tn = (int)(l / 56u);
+      tm = (int)(su * 56u + l % 56u);
+    } else {
+      // (units that do not divide 56, and the last row tiles of a launch: the last unit may be short) unit x column tiles
+      const unsigned o2 = orig - full * tnn, unit = u_t * tnn;
+      const unsigned u = o2 / unit, l = o2 - u * unit;
+      const unsigned left = tiles_m - full - u * u_t, ul = left < u_t ? left : u_t;
+      tn = (int)(l / ul);
+      tm = (int)(full + u * u_t + l % ul);
+    }
+  } else if (p.cluster > 1) {
     // clustered form: the tiles of a group wait for each other, so they take CONSECUTIVE block ids (dispatched together);
     // XCD placement (round-robin over block ids: speed only, never correctness) keeps a row tile's column tiles together
     const unsigned c = (unsigned)p.cluster, tnn = (unsigned)p.tiles_n;
@@ -75,7 +98,9 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
   }
   const int m0 = tm * p.tile_rows;
   const int n0 = tn * L_BN;
-  const int used = m0 + p.tile_rows <= p.M ? p.tile_rows : p.M - m0;   // rows of this tile that exist (one group)
+  // rows of this tile that exist: one group, or one member of a cluster; the packed form: rows of one or two groups (the
+  // staging below decodes every row's own frame, so a tile may start and end anywhere in a frame)
+  const int used = m0 + p.tile_rows <= p.M ? p.tile_rows : p.M - m0;
 
   const char* __restrict__ x = p.x;
   const char* __restrict__ w = p.w;
@@ -202,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
   // The residual rows of the first three blocks are fetched BEFORE the reduction (48 registers through the main loop),
   // the next three when it ends: no memory latency is left in front of the first stores, and the rest land under them.
   const int col = n0 + wave * 32 + lr;
-  const float inv_n = 1.f / (float)p.tile_rows;   // (a tile holds exactly one group, or one member of a cluster)
+  const float inv_n = 1.f / (float)p.tile_rows;   // (a tile holds exactly one group, or one member of a cluster; packed: unused)
   const int lim = used - 4 * lh;   // block-local row offsets below this one exist
   // the residual runs of a block: staged row rl0 (+ 16) of the block, columns 8 * grp .. + 7 of the wave's 32
   const int rl0 = lane >> 2, grp = lane & 3;
@@ -285,25 +310,133 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
     res_fetch(std::integral_constant<int, 4>{});
     res_fetch(std::integral_constant<int, 5>{});
   }
-  float s1 = 0.f;
+  // The packed form's tile may hold rows of two groups, the boundary at row 112: blocks 0 .. 2 and elements e < 8 of block 3
+  // (rows 96 .. 111) are the first segment - static per accumulator element, no selects.  A tile without a boundary adds
+  // its two halves' sums up (one segment); the unpacked form keeps its one sequential sum (the bits it always gave).
+  const int seg0 = p.packed ? (int)min((long long)used, (m0 / p.rows_per_group + 1ll) * p.rows_per_group - m0) : used;
+  const bool shared = seg0 < used;   // (block-uniform) two segments, 112 rows each
+  float mean, mean_b, s2, s2b = 0.f;
+  if (p.packed) {
+    float s1 = 0.f, s1b = 0.f;
 #pragma unroll
-  for (int mt = 0; mt < L_MT; ++mt)
+    for (int mt = 0; mt < L_MT; ++mt)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) s1 += acc[mt][e];
-  s1 += __shfl_xor(s1, 32, 64);
-  const float mean = s1 * inv_n;
-  float s2 = 0.f;
+      for (int e = 0; e < 16; ++e) {
+        if (mt < 3 || (mt == 3 && e < 8))
+          s1 += acc[mt][e];
+        else
+          s1b += acc[mt][e];
+      }
+    s1 += __shfl_xor(s1, 32, 64);
+    s1b += __shfl_xor(s1b, 32, 64);
+    const float inv0 = 1.f / (float)seg0, inv1 = 1.f / (float)(shared ? used - seg0 : seg0);   // (uniform)
+    mean = (shared ? s1 : s1 + s1b) * inv0;
+    mean_b = shared ? s1b * inv1 : mean;
+    s2 = 0.f;
 #pragma unroll
-  for (int mt = 0; mt < L_MT; ++mt)
+    for (int mt = 0; mt < L_MT; ++mt)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
-      const float d = acc[mt][e] - mean;
-      s2 = roff < lim ? fmaf(d, d, s2) : s2;
-    }
-  s2 += __shfl_xor(s2, 32, 64);
+      for (int e = 0; e < 16; ++e) {
+        const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+        if (mt < 3 || (mt == 3 && e < 8)) {
+          const float d = acc[mt][e] - mean;
+          s2 = roff < lim ? fmaf(d, d, s2) : s2;
+        } else {
+          const float d = acc[mt][e] - mean_b;
+          s2b = roff < lim ? fmaf(d, d, s2b) : s2b;
+        }
+      }
+    s2 += __shfl_xor(s2, 32, 64);
+    s2b += __shfl_xor(s2b, 32, 64);
+    if (!shared) s2 += s2b;
+  } else {
+    float s1 = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < L_MT; ++mt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) s1 += acc[mt][e];
+    s1 += __shfl_xor(s1, 32, 64);
+    mean = mean_b = s1 * inv_n;
+    s2 = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < L_MT; ++mt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+        const float d = acc[mt][e] - mean;
+        s2 = roff < lim ? fmaf(d, d, s2) : s2;
+      }
+    s2 += __shfl_xor(s2, 32, 64);
+  }
   float g_mean = mean, g_var = s2 * inv_n;
-  if (p.cluster > 1) {
+  float g_mean_b = 0.f, g_var_b = 0.f;   // the shared tile's second group
+  if (p.packed) {
+    // ---- the packed form's exchange: the protocol of the unpacked one below (value | epoch in one agent-scope store, every
+    // wave publishes - both segments - before it polls, a bounded poll, p.xerr), one granule per lane and SEGMENT: slot
+    // [tile][column tile][wave][segment][lane].  A tile gathers, for each of its one or two groups, the group's segment of
+    // every tile the group touches and merges them by Chan's update in tile order, the row counts (112 or 224) taken from
+    // the geometry.  ONE copy of the merge code runs for both groups of a shared tile (a loop that is not unrolled): every
+    // tile of a group applies the same instructions to the same operands in the same order -> the same bits.
+    const long long gstride = (long long)p.tiles_n * 4 * 2 * 64;   // granules between consecutive row tiles
+    // (a uniform base + the lane: the loads and stores take the base from scalar registers)
+    unsigned long long* const cbase = p.xchg + ((long long)tn * 4 + wave) * 2 * 64;
+    unsigned long long* slot = cbase + tm * gstride + lane;
+    __hip_atomic_store(slot, ((unsigned long long)p.epoch << 32) | (unsigned long long)__float_as_uint(lh ? s2 : mean),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (shared)
+      __hip_atomic_store(slot + 64, ((unsigned long long)p.epoch << 32) | (unsigned long long)__float_as_uint(lh ? s2b : mean_b),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const long long rpg = p.rows_per_group;
+    const long long g0 = m0 / rpg;
+#pragma unroll 1
+    for (int sg = 0; sg <= (shared ? 1 : 0); ++sg) {
+      const long long f0 = (g0 + sg) * rpg;                        // the group's rows f0 .. f0 + rpg - 1
+      const int tf = (int)(f0 / L_ROWS), tl = (int)((f0 + rpg - 1) / L_ROWS);
+      float n = 0.f, mu = 0.f, m2 = 0.f;
+      for (int j0 = tf; j0 <= tl; j0 += 4) {
+        // four granules in flight at once (one latency for the usual four tiles of a group), then each is verified and - only
+        // if its tag is not this launch's yet - polled on.  The tile's own granule is read back like a partner's (the same
+        // bits): its statistics need not stay in registers through the merge.
+        unsigned long long g[4];
+        // tile j's granule of this group (a scalar offset): segment 1 where the group starts inside the tile
+        auto granule = [&](int j) { return cbase + (j * gstride + ((long long)j * L_ROWS < f0 ? 64 : 0)) + lane; };
+#pragma unroll
+        for (int u = 0; u < 4; ++u)   // (past the group: a valid address, unused)
+          g[u] = __hip_atomic_load(granule(j0 + u <= tl ? j0 + u : tm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int j = j0 + u;
+          if (j > tl) break;
+          const long long lo = max(f0, (long long)j * L_ROWS), hi = min(f0 + rpg, (long long)(j + 1) * L_ROWS);
+          const float nt = (float)(hi - lo);
+          bool ok = (unsigned)(g[u] >> 32) == p.epoch;
+#pragma unroll 1
+          for (int spin = 0; spin < (1 << 20) && __builtin_amdgcn_read_exec() != __builtin_amdgcn_ballot_w64(ok); ++spin) {
+            __builtin_amdgcn_s_sleep(8);
+            g[u] = __hip_atomic_load(granule(j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ok = (unsigned)(g[u] >> 32) == p.epoch;
+          }
+          if (__builtin_amdgcn_read_exec() != __builtin_amdgcn_ballot_w64(ok) && lane == 0) atomicAdd(p.xerr, 1u);
+          const float v = __uint_as_float((unsigned)g[u]);
+          const float o = __shfl_xor(v, 32, 64);
+          const float mj = lh ? o : v, qj = lh ? v : o;
+          // Chan's update in tile order: the same operands in the same order on every tile of the group -> the same bits
+          const float tot = n + nt, delta = mj - mu;
+          mu += delta * (nt / tot);
+          m2 += qj + delta * delta * (n * nt / tot);
+          n = tot;
+        }
+      }
+      const float gv = m2 / n;
+      if (sg) {
+        g_mean_b = mu;
+        g_var_b = gv;
+      } else {
+        g_mean = mu;
+        g_var = gv;
+      }
+    }
+  } else if (p.cluster > 1) {
     // ---- one exchange with the other tiles of the group (same columns): lane (lr, lh) publishes the tile's mean (lh = 0) or
     // centred sum of squares (lh = 1) of column lr as an 8-byte {value, epoch} granule - ONE agent-scope store, untorn, so
     // the tag IS the flag: no fence, no separate flag word - then reads the same granule of every partner until its tag is
@@ -357,10 +490,18 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
   }
   const float sc = p.gamma[col] / sqrtf(g_var + p.eps);
   const float sf = p.beta[col] - g_mean * sc;
+  float sc_b = sc, sf_b = sf;   // rows 112 .. 223: the shared tile's second (scale, shift) pair, else the same
+  if (shared) {
+    sc_b = p.gamma[col] / sqrtf(g_var_b + p.eps);
+    sf_b = p.beta[col] - g_mean_b * sc_b;
+  }
 #pragma unroll
   for (int mt = 0; mt < L_MT; ++mt)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[mt][e] = fmaf(acc[mt][e], sc, sf);
+    for (int e = 0; e < 16; ++e) {
+      const bool first = mt < 3 || (mt == 3 && e < 8);   // (static per element)
+      acc[mt][e] = fmaf(acc[mt][e], first ? sc : sc_b, first ? sf : sf_b);
+    }
   const bool relu = p.act == AVS_ACT_RELU;
 
   __syncthreads();   // every wave has read its last fragments: the staging regions alias the operand buffers
@@ -415,13 +556,19 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
 
 // The shapes the 224-row form takes: AVS_F16X2, one group of 193 .. 224 rows per tile, cout in multiples of 128, a
 // reduction walked by the scalar tap walk in 64-byte steps inside the 2 GiB buffer window, the caller not asking for
-// another tile (avs_conv_desc.variant: AVS_TILE_AUTO or AVS_TILE_224).
+// another tile (avs_conv_desc.variant: AVS_TILE_AUTO or AVS_TILE_224).  The packed clustered form (AVS_CLUSTER_PACKED): tiles
+// of 224 consecutive rows, groups of a multiple of 112 rows.
 bool igemm_h2_local224_ok(const IgemmParams& p, int dtype, long long lin_stride) {
   const int tile_mode = p.variant & 3;
   if (dtype != AVS_F16X2 || !(tile_mode == AVS_TILE_AUTO || tile_mode == AVS_TILE_224)) return false;
   if (p.variant & AVS_STAGING_GENERIC) return false;
   const int cl = p.cluster > 1 ? p.cluster : 1;
-  if (p.tile_rows * cl != p.rows_per_group || p.tile_rows <= 192 || p.tile_rows > L_ROWS) return false;
+  if (p.packed) {
+    // (bncluster_plan: 224 consecutive rows per tile, groups of a multiple of 112 rows)
+    if (p.tile_rows != L_ROWS || p.cluster <= 1 || p.rows_per_group < L_ROWS || p.rows_per_group % (L_ROWS / 2) != 0) return false;
+  } else if (p.tile_rows * cl != p.rows_per_group || p.tile_rows <= 192 || p.tile_rows > L_ROWS) {
+    return false;
+  }
   if (p.N % L_BN != 0 || p.M % p.rows_per_group != 0) return false;
   if (p.cin % L_STEP != 0 || p.K % L_STEP != 0 || p.K % p.cin != 0 || p.K / p.cin > 32) return false;
   return igemm_buffer_window_ok(p, lin_stride, 4, L_BN);

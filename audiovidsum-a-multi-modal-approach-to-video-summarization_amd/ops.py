@@ -288,11 +288,12 @@ def conv_bnlocal_tile_rows(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, 
 
 
 def conv_bncluster_ok(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x_img_stride, x_row_stride, x_px_stride,
-                      w_row_stride, y_px_stride, rows_per_group, cluster):
+                      w_row_stride, y_px_stride, rows_per_group, cluster, packed=False):
     """Does the library take this convolution + BatchNorm as ONE launch with groups of `cluster` tiles (the clustered
-    tile-local form, avs_conv2d_nhwc_bncluster)?"""
+    tile-local form, avs_conv2d_nhwc_bncluster)?  packed: in its packed form (AVS_CLUSTER_PACKED: tiles of 224 consecutive
+    rows, groups of a multiple of 112 rows)?"""
     d = _abi.ConvDesc(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x_img_stride, x_row_stride,
-                      x_px_stride, w_row_stride, y_px_stride, ACT_NONE, 1.0)
+                      x_px_stride, w_row_stride, y_px_stride, ACT_NONE, 1.0, 0, _abi.CLUSTER_PACKED if packed else 0)
     r = lib().avs_conv2d_bncluster_workspace_bytes(ctypes.byref(d), int(rows_per_group), int(cluster))
     if r == _abi.E_UNSUPPORTED:
         return False
@@ -365,7 +366,8 @@ def _stats_workspace(device, nbytes):
 
 def conv2d_raw(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x, x_img_stride, x_row_stride, x_px_stride,
                wt, w_row_stride, y, y_px_stride, bias=None, act=ACT_NONE, alpha=1.0, x_off=0, y_off=0, algo_k=None,
-               bnstats=None, bnlocal=None, algo_in_elems=None, w_layout=0, variant=0, cluster=1, x_affine=None):
+               bnstats=None, bnlocal=None, algo_in_elems=None, w_layout=0, variant=0, cluster=1, x_affine=None,
+               packed=False):
     """algo_k: the algorithmic reduction length when it differs from kh*kw*cin (zero-padded stem rows);
     algo_in_elems: input elements the launch reads when the geometry does not say (the re-viewed stem image).
     bnstats = (rows_per_group, gamma, beta, eps): the BatchNorm batch statistics of equal-sized row groups from the
@@ -374,6 +376,7 @@ def conv2d_raw(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x, x_i
     bnlocal = (rows_per_group, gamma, beta, eps, residual2d | None): the whole BatchNorm (+ residual, then `act`) in
     the convolution's launch (avs_conv2d_nhwc_bnlocal; shapes for which conv_bnlocal_tile_rows is not None).
     cluster > 1 (with bnlocal): a group = `cluster` tiles (avs_conv2d_nhwc_bncluster: AVS_F16X2, 14x14 maps).
+    packed (with cluster > 1): its packed form, tiles of 224 consecutive rows (variant | _abi.CLUSTER_PACKED).
     w_layout: _abi.AVS_W_ROWS (wt[cout, K]) or AVS_W_KSTEP32 (the image weights_kstep32() makes).
     variant: avs_conv_desc.variant (_abi.TILE_128 / TILE_256 | STAGING_GENERIC): a per-call override of the tile /
     staging choice, for tests and the study tools (the library has no global tuning state).
@@ -386,6 +389,10 @@ def conv2d_raw(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x, x_i
             raise ValueError("an AVS_F16P8 input is taken by the convolution + statistics form (bnstats=...)")
         x, formats = x.data, _abi.X_F16P8
     _dev(x, wt, y, bias)
+    if packed:
+        if bnlocal is None or cluster <= 1:
+            raise ValueError("packed is a form of the clustered BatchNorm (bnlocal=..., cluster > 1)")
+        variant = int(variant) | _abi.CLUSTER_PACKED
     d = _abi.ConvDesc(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x_img_stride, x_row_stride,
                       x_px_stride, w_row_stride, y_px_stride, act, float(alpha), int(w_layout), int(variant), formats)
     flops = 2.0 * n * ho * wo * cout * (algo_k if algo_k is not None else kh * kw * cin)
@@ -415,7 +422,7 @@ def conv2d_raw(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x, x_i
                                                 int(epoch), _stream()),
                 "avs_conv2d_nhwc_bncluster"),
                    cbytes + (float(es) * n * ho * wo * cout if residual is not None else 0.0),
-                   form=f"clustered tile-local BatchNorm {kh}x{kw}")
+                   form=f"{'packed ' if packed else ''}clustered tile-local BatchNorm {kh}x{kw}")
             return None
         _timed("conv", dtype, flops, lambda: check(
             lib().avs_conv2d_nhwc_bnlocal(ctypes.byref(d), _p(x, x_off), _p(wt), _p(y, y_off), int(rpg), _p(gamma),

@@ -134,7 +134,9 @@ typedef struct {
                              * stride-1 'same' layers - 3x3 under the BatchNorm epilogues, any KH x KW under bias + ReLU -
                              * on the tap-major walk instead of the shifted-row form);
                              * AVS_STAGING_GENERIC (bit 2): the general per-lane gather staging even where
-                             * the scalar tap walk applies.  Results do not depend on it beyond fp32 summation order. */
+                             * the scalar tap walk applies; AVS_CLUSTER_PACKED (bit 3): the packed form of
+                             * avs_conv2d_nhwc_bncluster (see there; every other entry point ignores the bit).
+                             * Results do not depend on it beyond fp32 summation order.                        */
   int formats;              /* 0, or AVS_F16P8 operands of the AVS_F16X2 1x1 forms (bits): AVS_X_F16P8 - the INPUT of
                              * avs_conv2d_nhwc_bnstats (1x1 / stride 1 on dense rows, cin a multiple of 32, >= 64);
                              * AVS_Y_F16P8 / AVS_RES_F16P8 - the OUTPUT / the RESIDUAL of avs_conv2d_nhwc_affine (cout and
@@ -143,7 +145,8 @@ typedef struct {
 } avs_conv_desc;
 enum { AVS_W_ROWS = 0, AVS_W_KSTEP32 = 1 };
 enum { AVS_X_F16P8 = 1, AVS_Y_F16P8 = 2, AVS_RES_F16P8 = 4 };
-enum { AVS_TILE_AUTO = 0, AVS_TILE_128 = 1, AVS_TILE_256 = 2, AVS_TILE_224 = 3, AVS_STAGING_GENERIC = 4 };
+enum { AVS_TILE_AUTO = 0, AVS_TILE_128 = 1, AVS_TILE_256 = 2, AVS_TILE_224 = 3, AVS_STAGING_GENERIC = 4,
+       AVS_CLUSTER_PACKED = 8 };
 
 int avs_conv2d_nhwc(const avs_conv_desc* desc, const void* d_x, const void* d_w,
                     const float* d_bias, void* d_y, avs_stream_t stream);
@@ -213,6 +216,16 @@ int avs_conv2d_nhwc_bnlocal(const avs_conv_desc* desc, const void* d_x, const vo
  * complete groups then always finish and free the CUs the next groups need.  When several queues feed the chip at once with
  * kernels of this kind - two streams, or processes time-sharing one GPU - each can hold partial groups that keep the other's
  * partners out; the bounded waits then end the launch and the counter says so (observed with 4 processes on one GPU).
+ * desc->variant & AVS_CLUSTER_PACKED: the packed form.  Tiles are 224 CONSECUTIVE rows of the launch whatever
+ * rows_per_group is, so no tile runs a 32-row block for 4 live rows: groups of 784 rows (four 14x14 maps) take 7 full tiles
+ * per 2 groups instead of 8 of 196 rows, groups of 3136 rows (four 28x28 maps) 14 instead of 16.  A tile meets at most two
+ * groups, the boundary inside it at row 112 only: rows_per_group >= 224 and = 0 or 112 (mod 224), a group touching at most
+ * 16 tiles; `cluster` and every other condition as without the bit (AVS_E_UNSUPPORTED otherwise: the caller keeps the
+ * unpacked form).  Each tile publishes one granule per lane and segment (its rows inside one group) and merges the segments
+ * of its group - or of both its groups - in tile order with their row counts: the same bits on every tile of a group,
+ * deterministic.  The workspace holds two granules per lane and tile of 224 rows (ask with the same desc).  The tiles that
+ * wait for each other - one group's, or two groups' around their shared tile: at most 31 - take consecutive block ids, under
+ * the same single-queue assumption.  Sums run in another fixed order than the unpacked form's: equal to rounding.
  * d_xchg: avs_conv2d_bncluster_workspace_bytes(...) bytes, 64-byte aligned, ZEROED ONCE by the caller when allocated and
  * then left alone; epoch: a value that is new for this buffer on every call (1, 2, 3, ...; never 0) - granules of earlier
  * calls are then recognisably stale, nothing needs clearing between calls.

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Kernel study, AVS_F16X2: what each epilogue form costs on top of the plain contraction, per ResNet-50 layer shape.
 plain = avs_conv2d_nhwc (raw output), stats = avs_conv2d_nhwc_bnstats, local = avs_conv2d_nhwc_bnlocal (without / with
-residual), affine = avs_conv2d_nhwc_affine (with residual).  Usage: python tools/h2_forms_study.py [--n 4096]"""
+residual), affine = avs_conv2d_nhwc_affine (with residual), cluster4 / packed4 = avs_conv2d_nhwc_bncluster on 4-frame groups
+without / with AVS_CLUSTER_PACKED.  Usage: python tools/h2_forms_study.py [--n 4096]"""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -80,6 +81,15 @@ for name, hw, cin, cout, k, s in shapes:
             line += show("local+res/256", timed(lambda: ops.conv2d_raw(code, *geom, x, *xs, w, wrs, y, cout, act=ops.ACT_RELU,
                                                                        bnlocal=(rpg, gamma, beta, 1e-5, res), w_layout=1,
                                                                        variant=2)))
+    # 4-frame groups: the clustered form (one 196-row tile per map or map quarter) and its packed form (tiles of 224
+    # consecutive rows) side by side - the variant bit makes the A/B one process
+    rpg4 = 4 * rpg
+    if n % 4 == 0 and rpg % 196 == 0 and ops.conv_bncluster_ok(code, *geom, *xs, wrs, cout, rpg4, rpg4 // 196, packed=True):
+        for tag, r in (("", None), ("+res", res)):
+            for pk in (False, True):
+                line += show(("packed4" if pk else "cluster4") + tag, timed(lambda: ops.conv2d_raw(
+                    code, *geom, x, *xs, w, wrs, y, cout, act=ops.ACT_RELU, bnlocal=(rpg4, gamma, beta, 1e-5, r), w_layout=1,
+                    cluster=rpg4 // 196, packed=pk)))
     if k == 1 and cin * 4 > 128:
         groups = n
         sc, sh = torch.rand(groups, cout, device=dev) + 0.5, torch.randn(groups, cout, device=dev)

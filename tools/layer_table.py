@@ -8,7 +8,7 @@ Per layer: time per pass, matrix rate (algorithmic FLOP / time), stream rate (bf
 time) and the time an ideal kernel would take: max(FLOP / 1.2 PFLOP/s, bytes / 5.5 TB/s) - 1.2 PF is what the LDS-DMA
 intake allows a 128x128-tile contraction here, 5.5 TB/s what a streaming kernel reaches on this chip.
 
-Usage: python tools/layer_table.py [--n 8192] [--gf 1] [--dtype bf16|f32split]"""
+Usage: python tools/layer_table.py [--n 8192] [--gf 1] [--dtype bf16|f32split|f16x2] [--pack on|off|ab]"""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -22,6 +22,8 @@ ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32split", "f32", "
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--set", action="append", default=[], help="runner attribute override, e.g. --set gram_finish_min_k=64")
 ap.add_argument("--p8", default="on", choices=["on", "off"], help="f16x2: AVS_F16P8 storage of the inner block outputs of layers 1-2")
+ap.add_argument("--pack", default="on", choices=["on", "off", "ab"],
+                help="f16x2, --gf 4: the packed clustered BatchNorm on / off, or ab: off, on, off in one run and a comparison of the cluster rows")
 ap.add_argument("--short", type=int, default=0,
                 help="study build (AVS_STUDY_LIB=1): reductions of at most this many bytes per row take 64-byte steps (rule: 2048)")
 args = ap.parse_args()
@@ -157,35 +159,65 @@ def timed_stem_h2(frames_u8, *a, **kw):
 ops.stem_conv_pool_h2 = timed_stem_h2
 ops.bn_gram_affine = timed_op(ops.bn_gram_affine, "gram")
 ops.conv1x1_affine = timed_op(ops.conv1x1_affine, "affine")
-for _ in range(2):
-    runner.forward(frames, gf)
-torch.cuda.synchronize()
-acc = None
-for _ in range(args.reps):
-    records.clear()
-    t0, t1 = ev(), ev()
-    t0.record()
-    runner.forward(frames, gf)
-    t1.record()
+
+
+def measure(label):
+    """One table of the pass as the runner's switches stand -> {(layer, form): ms}."""
+    for _ in range(2):
+        runner.forward(frames, gf)
     torch.cuda.synchronize()
-    ms = [r[4].elapsed_time(r[5]) for r in records]
-    acc = ms if acc is None else [min(a, b) for a, b in zip(acc, ms)]
-    total = t0.elapsed_time(t1)
-print(f"{args.n} frames, groups of {args.gf}, {args.dtype}: forward {total:.1f} ms = {args.n / total * 1e3:.0f} frames/s "
-      f"(events between layers cost a few %)")
-print(f"{'layer':34s} {'form':11s} {'ms':>8s} {'TFLOP/s':>8s} {'TB/s':>6s} {'ideal ms':>8s} {'x ideal':>7s} {'excess ms':>9s}")
-tsum = isum = 0.0
-agg = {}
-for (name, form, flops, byts, _, _), ms in zip(records, acc):
-    ideal = max(flops / MFMA_IDEAL, byts / 5.5e12) * 1e3
-    tsum += ms
-    isum += ideal
-    k = (name, form)
-    a = agg.setdefault(k, [0, 0.0, 0.0, flops, byts])
-    a[0] += 1
-    a[1] += ms
-    a[2] += ideal
-for (name, form), (cnt, ms, ideal, flops, byts) in agg.items():
-    print(f"{(str(cnt) + ' x ' + name):34s} {form:11s} {ms:8.2f} {flops * cnt / ms / 1e9:8.0f} {byts * cnt / ms / 1e9:6.2f} "
-          f"{ideal:8.2f} {ms / ideal:7.2f} {ms - ideal:9.2f}")
-print(f"{'sum of layers':46s} {tsum:8.2f} {'':15s} {isum:8.2f} {tsum / isum:7.2f} {tsum - isum:9.2f}")
+    acc = None
+    for _ in range(args.reps):
+        records.clear()
+        t0, t1 = ev(), ev()
+        t0.record()
+        runner.forward(frames, gf)
+        t1.record()
+        torch.cuda.synchronize()
+        ms = [r[4].elapsed_time(r[5]) for r in records]
+        acc = ms if acc is None else [min(a, b) for a, b in zip(acc, ms)]
+        total = t0.elapsed_time(t1)
+    print(f"{label}{args.n} frames, groups of {args.gf}, {args.dtype}: forward {total:.1f} ms = {args.n / total * 1e3:.0f} frames/s "
+          f"(events between layers cost a few %)")
+    print(f"{'layer':34s} {'form':11s} {'ms':>8s} {'TFLOP/s':>8s} {'TB/s':>6s} {'ideal ms':>8s} {'x ideal':>7s} {'excess ms':>9s}")
+    tsum = isum = 0.0
+    agg = {}
+    for (name, form, flops, byts, _, _), ms in zip(records, acc):
+        ideal = max(flops / MFMA_IDEAL, byts / 5.5e12) * 1e3
+        tsum += ms
+        isum += ideal
+        k = (name, form)
+        a = agg.setdefault(k, [0, 0.0, 0.0, flops, byts])
+        a[0] += 1
+        a[1] += ms
+        a[2] += ideal
+    for (name, form), (cnt, ms, ideal, flops, byts) in agg.items():
+        print(f"{(str(cnt) + ' x ' + name):34s} {form:11s} {ms:8.2f} {flops * cnt / ms / 1e9:8.0f} {byts * cnt / ms / 1e9:6.2f} "
+              f"{ideal:8.2f} {ms / ideal:7.2f} {ms - ideal:9.2f}")
+    print(f"{'sum of layers':46s} {tsum:8.2f} {'':15s} {isum:8.2f} {tsum / isum:7.2f} {tsum - isum:9.2f}")
+    print(f"{'sum of the cluster rows':46s} {sum(v[1] for k, v in agg.items() if k[1] == 'cluster'):8.2f}")
+    return {k: (v[0], v[1]) for k, v in agg.items()}
+
+
+if args.pack != "ab":
+    runner.pack_groups = args.pack == "on"
+    measure("")
+else:
+    # unpacked, packed, unpacked again in ONE process: the second unpacked table gives the tool's repeatability per row
+    tabs = []
+    for label, pack in (("[unpacked, 1st] ", False), ("[packed] ", True), ("[unpacked, 2nd] ", False)):
+        runner.pack_groups = pack
+        tabs.append(measure(label))
+        print()
+    u1, pk, u2 = tabs
+    print(f"{'cluster rows':34s} {'unpacked':>9s} {'again':>9s} {'repeat':>7s} {'packed':>9s} {'change':>7s}  (ms; unpacked = the faster of the two)")
+    su = sp = 0.0
+    for k, (cnt, ms) in pk.items():
+        if k[1] != "cluster":
+            continue
+        a, b = u1[k][1], u2[k][1]
+        base = min(a, b)
+        su += base
+        sp += ms
+        print(f"{(str(cnt) + ' x ' + k[0]):34s} {a:9.2f} {b:9.2f} {abs(a - b) / base * 100:6.1f}% {ms:9.2f} {(ms - base) / base * 100:+6.1f}%")
+    print(f"{'sum':34s} {su:9.2f} {'':9s} {'':7s} {sp:9.2f} {(sp - su) / su * 100:+6.1f}%")
