@@ -110,6 +110,39 @@ def resnet50_trunk_forward(sd, x, bn_mode="batch"):
     return F.adaptive_avg_pool2d(x, (1, 1)).flatten(1)
 
 
+def resnet50_trunk_trace(sd, x, bn_mode="batch"):
+    """resnet50_trunk_forward with every intermediate kept, in the dtype of sd and x -> (features [N,2048], OrderedDict).
+    Keys are torchvision's names: per convolution ("conv1", "layer1.0.conv2", "layer1.0.downsample", ...) name + ".raw"
+    (the convolution's output) and name (after its BatchNorm, and the ReLU where the net has one: not after a conv3 or
+    a downsample); "maxpool" (the pooled stem map); per bottleneck its name ("layer1.0": after the residual add and the
+    ReLU).  The same calls in the same order as resnet50_trunk_forward: in fp32 the features are equal bit for bit."""
+    from collections import OrderedDict
+    tr = OrderedDict()
+
+    def bn(t, p):
+        return bn_batch(t, sd[p + "weight"], sd[p + "bias"]) if bn_mode == "batch" else bn_eval(t, sd, p, 1e-5)
+
+    def conv_bn(name, t, w, pbn, stride=1, pad=0, relu=True):
+        tr[name + ".raw"] = raw = F.conv2d(t, sd[w], None, stride, pad)
+        tr[name] = y = torch.relu(bn(raw, pbn)) if relu else bn(raw, pbn)
+        return y
+
+    x = conv_bn("conv1", x, "0.weight", "1.", 2, 3)
+    tr["maxpool"] = x = F.max_pool2d(x, 3, 2, 1)
+    for li, (blocks, stride) in zip(range(4, 8), ((3, 1), (4, 2), (6, 2), (3, 2))):
+        for bi in range(blocks):
+            p, name = f"{li}.{bi}.", f"layer{li - 3}.{bi}"
+            s = stride if bi == 0 else 1
+            idn = x
+            y = conv_bn(name + ".conv1", x, p + "conv1.weight", p + "bn1.")
+            y = conv_bn(name + ".conv2", y, p + "conv2.weight", p + "bn2.", s, 1)
+            y = conv_bn(name + ".conv3", y, p + "conv3.weight", p + "bn3.", relu=False)
+            if p + "downsample.0.weight" in sd:
+                idn = conv_bn(name + ".downsample", x, p + "downsample.0.weight", p + "downsample.1.", s, relu=False)
+            tr[name] = x = torch.relu(y + idn)
+    return F.adaptive_avg_pool2d(x, (1, 1)).flatten(1), tr
+
+
 # ----------------------------------------------------------------------------- Inception-v3 (eval-mode BN)
 def _bc(sd, p, x, stride=1, padding=0):
     x = F.conv2d(x, sd[p + ".conv.weight"], None, stride, padding)
