@@ -204,7 +204,10 @@ __global__ __launch_bounds__(64 * NW, 512 / (64 * NW)) void flash_mhsa_h2q16_ker
 #pragma unroll
   for (int i = 0; i < DB; ++i) oacc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;
-  const float inv_sqrt_d = 1.f / sqrt_d;   // (head dims are powers of four: exact)
+  // head dims 64 and 256: sqrt_d = 8 and 16, the reciprocal exact.  Head dim 128: sqrtf(128) is rounded and so is its
+  // reciprocal, and the fp32 kernel above DIVIDES by sqrt_d where this one multiplies - a relative 2^-23 or so of the
+  // score between the two, held to float64 per kernel by tests/test_gpu_mhsa_f64.py
+  const float inv_sqrt_d = 1.f / sqrt_d;
 
   const int vkey = t & 31;
   const int vslot = 8 * ((vkey >> 2) & 3) + 4 * (vkey >> 4) + (vkey & 3);

@@ -194,7 +194,8 @@ def test_training_loop_matches_oracle(dev):
 
 
 @pytest.mark.parametrize("e,h,b,t", [(1024, 4, 1, 300), (512, 8, 2, 77), (64, 4, 3, 1), (1024, 4, 1, 1801),
-                                     (512, 4, 2, 33), (256, 4, 1, 129), (1024, 4, 2, 1), (1024, 4, 1, 5000)])
+                                     (512, 4, 2, 33), (256, 4, 1, 129), (1024, 4, 2, 1), (1024, 4, 1, 5000),
+                                     (512, 4, 1, 700)])   # head dim 128, 22 key tiles, the fp32 kernel's 4-wave instance
 def test_mhsa(dev, e, h, b, t):
     from avsum_amd.models.attention import MultiHeadSelfAttention
     from oracle import scorer as osc
