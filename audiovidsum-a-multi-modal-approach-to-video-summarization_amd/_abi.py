@@ -159,6 +159,9 @@ _SIGNATURES = {
     "avs_shot_cuts_batch": (c_int, [P, c_int64, P, c_int, c_double, c_double, c_int, P, P, P, P]),
     "avs_shot_tables_fill": (c_int, [P, c_int, P, P, P, P, P, c_int64, P, P, c_int64, P, c_int64, P, P]),
     "avs_gather_rows_u8": (c_int, [P, c_int64, c_int64, P, P, c_int64, P, P]),
+    "avs_shot_value_sums": (c_int, [P, c_int64, c_int, c_int64, P, c_int, P, P, c_int64, P, P]),
+    "avs_knapsack_batch_f64": (c_int, [P, c_int, c_int64, P, P, c_int, c_int, P, P, c_int64, P, c_int, P, P, P, P, P]),
+    "avs_mask_overlap_counts": (c_int, [P, P, c_int64, c_int, c_int64, P, c_int, P, P]),
 }
 
 _lib = None

@@ -12,7 +12,8 @@ from . import _abi
 from ._abi import (ACT_NONE, ACT_RELU, AVS_BF16, AVS_F16X2, AVS_F32, AVS_F32_SPLIT, BIAS_COL, BIAS_NONE, BIAS_ROW, check,
                    lib)
 from .ragged import (EVAL_CHUNK, EVAL_MAX_T, EVAL_TILE, FUSION_MAX_N, FUSION_MID_L, FUSION_SMALL_L,  # noqa: F401
-                     SHOT_INTERVAL, SHOT_MAX_FRAMES, SHOT_MICRO_BATCH, EvalTables, FusionTables, SeqTable, ShotTables)
+                     SHOT_INTERVAL, SHOT_MAX_FRAMES, SHOT_MICRO_BATCH, SUMMARY_MAX_CAPACITY, SUMMARY_MAX_ROWS, EvalTables,
+                     FusionTables, RaggedOffsets, SeqTable, ShotTables, SummaryTables)
 
 __all__ = [
     "ACT_NONE", "ACT_RELU", "linear", "gemm_nt_batched", "conv2d", "conv2d_raw", "conv2d_split", "conv_bnlocal_tile_rows", "conv_bncluster_ok", "conv_bnstats_ok", "cluster_exchange_errors", "lstm_split_errors", "conv1x1_bn", "conv1x1_gram_bn", "bn_gram_affine", "gram_supported", "frames_normalize", "pull_copy", "stem_conv_bn_pool", "stem_h2_operands", "stem_conv_pool_h2", "resize_bilinear",
@@ -21,6 +22,7 @@ __all__ = [
     "gather_scale", "FusionTables", "fusion_batch", "EvalTables", "eval_counts", "segment_mean_mask", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
     "SeqTable", "seq_shift_rows", "seq_mse",
     "ShotTables", "hsv_frame_diff_batch", "shot_cuts_batch", "shot_tables", "gather_rows",
+    "SummaryTables", "shot_value_sums", "knapsack_batch", "mask_overlap_counts",
 ]
 
 
@@ -1758,3 +1760,104 @@ def gather_rows(src, index, count, out=None):
     check(lib().avs_gather_rows_u8(_p(src), src.shape[0], row_bytes, _p(index), _p(count), cap, _p(out), _stream()),
           "avs_gather_rows_u8")
     return out
+
+
+# --------------------------------------------------------------------------- keyshot summaries
+def _summary_rows(scores, what):
+    """``scores`` [N] or [K, N] as its [K, N] view; K is limited to SUMMARY_MAX_ROWS."""
+    if isinstance(scores, torch.Tensor) and scores.dim() == 1:
+        scores = scores.unsqueeze(0)
+    if isinstance(scores, torch.Tensor) and scores.dim() == 2 and scores.shape[0] > SUMMARY_MAX_ROWS:
+        raise ValueError(f"{what}: {scores.shape[0]} score rows, a batch takes at most {SUMMARY_MAX_ROWS}")
+    return scores
+
+
+def _shot_table_args(tables, shot_offsets, shots, what):
+    _device_arg(shot_offsets, "shot_offsets", what, (torch.int64,), shape=(tables.nvideos + 1,), device=tables.device)
+    _device_arg(shots, "shots", what, (torch.int64,), ndim=2, device=tables.device)
+    if tuple(shots.shape) != (tables.shot_cap, 2):
+        raise ValueError(f"{what}: shots must have shape [{tables.shot_cap}, 2], the shot_cap of the tables, got "
+                         f"{list(shots.shape)}")
+
+
+def shot_value_sums(tables, scores, shot_offsets, shots):
+    """int64 [K, shot_cap] device tensor: for score row k and shot g the sum over the shot's frames of q(score) =
+    rint(clamp(score, 0, 1) * 2^32), exact in int64 (a shot's value is this sum over its length).  ``tables``: the
+    ops.SummaryTables of the batch; ``scores`` fp32 device [N] (K = 1) or [K, N] with unit column stride, N =
+    tables.frames; ``shot_offsets`` int64 [V + 1] and ``shots`` int64 [shot_cap, 2] (video-relative): the device tables
+    of ops.shot_tables, or a caller's in the same layout.  The entries past shot_offsets[V] are 0.  One launch, nothing
+    synchronises."""
+    what = "shot_value_sums"
+    _tables_arg(tables, SummaryTables, what)
+    scores = _summary_rows(scores, what)
+    _device_arg(scores, "scores", what, (torch.float32,), ndim=2, device=tables.device, contiguous=False)
+    if scores.shape[1] != tables.frames or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError(f"{what}: scores must hold {tables.frames} frames per row with unit stride, got shape "
+                         f"{list(scores.shape)} with strides {list(scores.stride())}")
+    _shot_table_args(tables, shot_offsets, shots, what)
+    k = scores.shape[0]
+    ld = scores.stride(0) if k > 1 else max(tables.frames, 1)
+    if ld < tables.frames:
+        raise ValueError(f"{what}: the rows of scores overlap (row stride {ld} for {tables.frames} frames)")
+    sums = torch.empty((k, tables.shot_cap), dtype=torch.int64, device=tables.device)
+    check(lib().avs_shot_value_sums(_p(scores), ld, k, tables.frames, _p(tables.offsets_t), tables.nvideos,
+                                    _p(shot_offsets), _p(shots), tables.shot_cap, _p(sums), _stream()),
+          "avs_shot_value_sums")
+    return sums
+
+
+def knapsack_batch(tables, sums, shot_offsets, shots):
+    """One 0/1 knapsack per (score row, video) in ONE launch: value = sums / length, weight = length, capacity =
+    tables.capacity, ties resolved as evaluation.keyshots.knapsack_host does (a shot is taken only where it is strictly
+    better).  ``sums``: int64 [K, shot_cap] of shot_value_sums.  Returns a dict of device tensors: ``picked`` uint8
+    [K, shot_cap], ``mask`` uint8 [K, N] (every frame written), ``optimum`` float64 [K, V], ``totals`` int64 [K, V, 3] =
+    (shots picked, frames picked, capacity).  Nothing synchronises."""
+    what = "knapsack_batch"
+    _tables_arg(tables, SummaryTables, what)
+    _device_arg(sums, "sums", what, (torch.int64,), shape=(None, tables.shot_cap), device=tables.device)
+    _shot_table_args(tables, shot_offsets, shots, what)
+    k, dev = sums.shape[0], tables.device
+    if k > SUMMARY_MAX_ROWS:
+        raise ValueError(f"{what}: {k} score rows, a batch takes at most {SUMMARY_MAX_ROWS}")
+    if tables.take_words(k) >= 1 << 31:
+        raise ValueError(f"{what}: the take-bit workspace of {k} rows x {tables.shot_cap} shots x {tables.words} words "
+                         "needs 2^31 entries or more")
+    take = torch.empty(max(tables.take_words(k), 1), dtype=torch.int64, device=dev)
+    picked = torch.empty((k, tables.shot_cap), dtype=torch.uint8, device=dev)
+    mask = torch.empty((k, tables.frames), dtype=torch.uint8, device=dev)
+    optimum = torch.empty((k, tables.nvideos), dtype=torch.float64, device=dev)
+    totals = torch.empty((k, tables.nvideos, 3), dtype=torch.int64, device=dev)
+    check(lib().avs_knapsack_batch_f64(_p(sums), k, tables.frames, _p(tables.offsets_t), _p(tables.capacity_t),
+                                       tables.nvideos, tables.max_capacity, _p(shot_offsets), _p(shots), tables.shot_cap,
+                                       _p(take), tables.words, _p(picked), _p(mask), _p(optimum), _p(totals), _stream()),
+          "avs_knapsack_batch_f64")
+    return {"picked": picked, "mask": mask, "optimum": optimum, "totals": totals}
+
+
+def mask_overlap_counts(tables_or_offsets, pred_mask, user_masks):
+    """int64 [V, U, 3] device tensor = per (video, user) the sums over the video's frames of (pred & user, pred, user):
+    what evaluation.keyshots.f1_from_overlap turns into the summary F1.  ``pred_mask`` uint8 [N] and ``user_masks``
+    uint8 [U, N] (unit column stride) on the device; ``tables_or_offsets``: an ops.SummaryTables, or the host frame
+    offsets [V + 1] (validated and uploaded).  One launch, nothing synchronises."""
+    what = "mask_overlap_counts"
+    _device_arg(pred_mask, "pred_mask", what, (torch.uint8,), ndim=1)
+    if isinstance(tables_or_offsets, SummaryTables):
+        tables = _tables_arg(tables_or_offsets, SummaryTables, what, pred_mask.device, pred_mask.shape[0])
+        offsets_t, nv = tables.offsets_t, tables.nvideos
+    else:
+        plan = RaggedOffsets(tables_or_offsets, what, device=pred_mask.device, rows=pred_mask.shape[0])
+        offsets_t, nv = plan.offsets_t, plan.count
+    n = pred_mask.shape[0]
+    _device_arg(user_masks, "user_masks", what, (torch.uint8,), shape=(None, n), device=pred_mask.device,
+                contiguous=False)
+    u = user_masks.shape[0]
+    if (n > 1 and user_masks.stride(1) != 1) or u > SUMMARY_MAX_ROWS:
+        raise ValueError(f"{what}: user_masks must hold at most {SUMMARY_MAX_ROWS} rows with unit column stride, got "
+                         f"shape {list(user_masks.shape)} with strides {list(user_masks.stride())}")
+    ld = user_masks.stride(0) if u > 1 else max(n, 1)
+    if ld < n:
+        raise ValueError(f"{what}: the rows of user_masks overlap (row stride {ld} for {n} frames)")
+    counts = torch.empty((nv, u, 3), dtype=torch.int64, device=pred_mask.device)
+    check(lib().avs_mask_overlap_counts(_p(pred_mask), _p(user_masks), ld, u, n, _p(offsets_t), nv, _p(counts),
+                                        _stream()), "avs_mask_overlap_counts")
+    return counts

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .evaluation.keyshots import keyshot_summaries_device
 from .evaluation.metrics import select_frames, select_mask_device
 
 
@@ -317,3 +318,11 @@ class FrameScoringPipeline:
         """The same selection as a uint8 device mask [N] (1 = selected), without downloading the scores: the per-video
         mean is summed on the device in numpy's order, so mask[a:b] is exactly select()'s indices of that video."""
         return select_mask_device(scores, video_offsets)
+
+    @staticmethod
+    def summarize_device(scores, video_offsets, shots, ratio=0.15):
+        """The keyshot summary of every video: whole shots chosen by a 0/1 knapsack (value = the shot's mean score,
+        weight = its length, capacity = ``ratio`` of the video), on the device.  ``shots``: the ShotBatchResult of
+        features.shots.detect_shots_batch, used where it lies, or one host [(start, end)] list per video.  Returns the
+        evaluation.keyshots.KeyshotResult: mask, picked, optimum and totals stay on the device until its host()."""
+        return keyshot_summaries_device(scores, video_offsets, shots, ratio)

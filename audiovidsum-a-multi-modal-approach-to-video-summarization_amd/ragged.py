@@ -1,5 +1,6 @@
 """Host plans of the ragged-batch layers: row offsets validated on the host and uploaded once (RaggedOffsets and the
-three tables built on it - EvalTables, SeqTable, ShotTables) and the pair tables of the batched fusion (FusionTables).
+four tables built on it - EvalTables, SeqTable, ShotTables, SummaryTables) and the pair tables of the batched fusion
+(FusionTables).
 Pure host code on numpy and torch: nothing here touches the kernel library, so the plans can be built and checked with
 ``device="cpu"`` where there is no GPU.  ops.py re-exports every name and holds the launch wrappers that take them."""
 import numpy as np
@@ -17,6 +18,11 @@ EVAL_CHUNK = 1024        # columns it stages through LDS per step
 SHOT_INTERVAL = 3        # features/extractors.py FRAME_INTERVAL: the sampled frames are the multiples of 3,
 SHOT_MAX_FRAMES = 100    # MAX_FRAMES: at most 100 per shot,
 SHOT_MICRO_BATCH = 4     # MICRO_BATCH: in BatchNorm groups of 4 with a shorter tail group
+
+SUMMARY_MAX_CAPACITY = 8191   # knapsack cells 0 .. capacity: two fp64 rows of 8192 cells are 128 KiB of a CU's 160 KiB LDS
+SUMMARY_MAX_ROWS = 1024       # score rows of one knapsack batch (grid y).  The take-bit workspace holds rows * shot_cap *
+                              # words uint64 entries with words <= 128: below 2^31 for every shot_cap below 2^14 = 16 384
+                              # at the full 1024 rows and 8191 cells; past that the wrapper refuses by take_words itself
 
 
 def exclusive_offsets(lengths):
@@ -156,6 +162,46 @@ class ShotTables(RaggedOffsets):
         self.group_cap = int((thirds // SHOT_MICRO_BATCH + slots + 1).sum())
         self.packed_sizes = (4, 3 * (self.nvideos + 1), 2 * self.shot_cap, self.shot_cap + 1, self.group_cap + 1)
         self.cut_off_t, = _upload(self.device, self.cut_off)
+
+
+class SummaryTables(RaggedOffsets):
+    """The host plan of one batch layout for the keyshot summaries (shot_value_sums, knapsack_batch,
+    mask_overlap_counts), built once from the host frame offsets [V + 1] of the videos in the concatenated scores, the
+    summary ``ratio`` and ``shot_cap``, the rows of the shot table the kernels will be given (an int, or a ShotTables
+    whose shot_cap is taken).
+
+    Host side (numpy): ``offsets``, ``lengths``, ``nvideos``, ``frames`` (= offsets[-1]), ``ratio``, ``capacity`` int64 [V]
+    = int(floor(float64(n_v) * float64(ratio))), the frames a summary of video v may hold - computed HERE and never on
+    the device - ``max_capacity``, ``shot_cap``, ``words`` = ceil((max_capacity + 1) / 64), the uint64 words of one
+    shot's take bits, and take_words(k).  Device side: ``offsets_t``, ``capacity_t``.  ``device="cpu"`` keeps everything
+    on the host (the builder can be checked without a GPU).  Refused, each with a ValueError: what ShotTables refuses
+    about the offsets, a ratio that is not finite or lies outside (0, 1], a capacity above 8191 (the LDS-resident
+    limit), shot_cap < 1."""
+
+    def __init__(self, offsets_host, ratio=0.15, shot_cap=1, device=None):
+        super().__init__(offsets_host, "SummaryTables", device=device, max_total=1 << 24, total_inclusive=True)
+        ratio = float(ratio)
+        if not (np.isfinite(ratio) and 0.0 < ratio <= 1.0):
+            raise ValueError(f"SummaryTables: ratio must lie in (0, 1], got {ratio}")
+        if isinstance(shot_cap, ShotTables):
+            shot_cap = shot_cap.shot_cap
+        if int(shot_cap) < 1:
+            raise ValueError(f"SummaryTables: shot_cap must be >= 1, got {shot_cap}")
+        self.nvideos, self.frames, self.ratio, self.shot_cap = self.count, self.total, ratio, int(shot_cap)
+        self.capacity = np.floor(self.lengths.astype(np.float64) * np.float64(ratio)).astype(np.int64)
+        over = np.flatnonzero(self.capacity > SUMMARY_MAX_CAPACITY)
+        if over.size:
+            v = int(over[0])
+            raise ValueError(f"SummaryTables: video {v} has {int(self.lengths[v])} frames, a summary of "
+                             f"{int(self.capacity[v])} frames at ratio {ratio}, above the LDS-resident limit "
+                             f"{SUMMARY_MAX_CAPACITY}")
+        self.max_capacity = int(self.capacity.max())
+        self.words = (self.max_capacity + 1 + 63) // 64
+        self.capacity_t, = _upload(self.device, self.capacity)
+
+    def take_words(self, k):
+        """uint64 entries of the take-bit workspace [k][shot_cap][words] of a knapsack batch of ``k`` score rows."""
+        return int(k) * self.shot_cap * self.words
 
 
 class FusionTables:

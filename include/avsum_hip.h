@@ -857,6 +857,42 @@ int avs_shot_tables_fill(const int64_t* d_offsets, int nvideos, const int64_t* d
 int avs_gather_rows_u8(const uint8_t* d_src, int64_t src_rows, int64_t row_bytes, const int64_t* d_index,
                        const int64_t* d_count, int64_t capacity, uint8_t* d_out, avs_stream_t stream);
 
+/* ---- keyshot summaries: shot values, one 0/1 knapsack per (score row, video), summary overlap ------------------------
+ * (No counterpart in the reference: SURVEY Q17.  evaluation/keyshots.py holds the definitions and their numpy oracle.)
+ * The videos are the segments [offsets[v], offsets[v + 1]) of the concatenated frames, d_offsets int64 [nvideos + 1]
+ * (trusted: ops.SummaryTables guarantees it).  Video v's shots are the entries d_shot_offsets[v] .. d_shot_offsets[v + 1]
+ * of d_shots int64 [shot_cap, 2] = video-relative (start, end), the layout avs_shot_tables_fill writes; a shot is
+ * clipped to its video.  Integers, or fp64 values a fixed recurrence defines: two calls on the same input give the same
+ * bytes.  No float atomics; no entry point allocates, synchronises or reads a result back.                           */
+
+/* d_sums int64 [nrows, shot_cap]: d_sums[k, g] = sum over the frames r of shot g of q(d_scores[k * ld_scores + base_v +
+ * r]), q(x) = rint(clamp(x, 0, 1) * 2^32) in fp64 (round half to even; NaN -> 0).  The entries from
+ * d_shot_offsets[nvideos] on get 0.  One wave per (k, shot), 16-byte loads from the first aligned score on.           */
+int avs_shot_value_sums(const float* d_scores, int64_t ld_scores, int nrows, int64_t n, const int64_t* d_offsets,
+                        int nvideos, const int64_t* d_shot_offsets, const int64_t* d_shots, int64_t shot_cap,
+                        int64_t* d_sums, avs_stream_t stream);
+
+/* One 0/1 knapsack per (k, v), one workgroup of 1024 threads each: shot i of video v has weight w_i = end - start and
+ * value double(sum_i) / double(w_i); the capacity is d_capacity[v] (int64 [nvideos], at most max_capacity <= 8191).
+ * row[w] = max over "skip" and, where w >= w_i, row'[w - w_i] + value, the shot TAKEN only where that is strictly
+ * greater; both fp64 rows live in LDS (128 KiB of a CU's 160 KiB).  The take bits of shot g =
+ * d_shot_offsets[v] + i are written as uint64 words (bit w & 63 of word w >> 6) to d_take [nrows][shot_cap][words],
+ * words >= ceil((max_capacity + 1) / 64); the backtrack starts at w = capacity with the last shot.
+ * d_picked uint8 [nrows, shot_cap] (1 = in the summary; written for the shots below d_shot_offsets[nvideos]),
+ * d_mask uint8 [nrows, n] (EVERY frame of every video is written, 0 or 1), d_optimum fp64 [nrows, nvideos],
+ * d_totals int64 [nrows, nvideos, 3] = (shots picked, frames picked, capacity).  A video without shots gets an
+ * all-zero mask, optimum 0 and totals (0, 0, capacity).                                                              */
+int avs_knapsack_batch_f64(const int64_t* d_sums, int nrows, int64_t n, const int64_t* d_offsets,
+                           const int64_t* d_capacity, int nvideos, int max_capacity, const int64_t* d_shot_offsets,
+                           const int64_t* d_shots, int64_t shot_cap, uint64_t* d_take, int words, uint8_t* d_picked,
+                           uint8_t* d_mask, double* d_optimum, int64_t* d_totals, avs_stream_t stream);
+
+/* d_counts int64 [nvideos, nusers, 3] = (tp, n_pred, n_user) over the frames of video v: the sums of pred & user, pred
+ * and user with d_pred_mask uint8 [n] and d_user_masks uint8 [nusers, n] (row stride ld_user), a byte counting as 1
+ * when it is not 0.  One workgroup per (video, user).                                                                */
+int avs_mask_overlap_counts(const uint8_t* d_pred_mask, const uint8_t* d_user_masks, int64_t ld_user, int nusers,
+                            int64_t n, const int64_t* d_offsets, int nvideos, int64_t* d_counts, avs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
