@@ -162,6 +162,8 @@ _SIGNATURES = {
     "avs_shot_value_sums": (c_int, [P, c_int64, c_int, c_int64, P, c_int, P, P, c_int64, P, P]),
     "avs_knapsack_batch_f64": (c_int, [P, c_int, c_int64, P, P, c_int, c_int, P, P, c_int64, P, c_int, P, P, P, P, P]),
     "avs_mask_overlap_counts": (c_int, [P, P, c_int64, c_int, c_int64, P, c_int, P, P]),
+    "avs_resize_bilinear_gather2_u8": (c_int, [P, c_int64, c_int, c_int, P, c_int64, P, c_int, c_int, P, c_int, c_int, P]),
+    "avs_segment_mean_perm_f32": (c_int, [P, c_int64, c_int64, c_int, P, c_int64, P, c_int, P, c_int64, P]),
 }
 
 _lib = None

@@ -105,6 +105,39 @@ class VisualFeatureExtractor(nn.Module):
             ops.segment_mean(inc, seg, out[:, 2048:])
         return out[0].cpu().numpy()
 
+    def embed_shots(self, frames_u8, plan):
+        """forward for every shot of a ragged batch of videos: fp32 [S, 4096] on the device, row s what forward returns
+        for the sampled frames of shot s of ``plan`` (an ops.StageOneTables; zeros for an empty shot).  ``frames_u8``:
+        device uint8 [N,h,w,3], the videos concatenated.  Per pass of the plan - whole BatchNorm groups of one size, so
+        both trunks take their uniform forms - the pass's frames are gathered (and resized to 224x224 and 299x299 by one
+        launch) straight from ``frames_u8``, and the two trunks write the pass's rows of one [F, 4096] buffer; two
+        segment_mean_perm launches then average every shot's rows, in the order of its frames.  The BatchNorm groups are
+        the ones forward builds shot by shot; only the summation order of their statistics may differ."""
+        ops._tables_arg(plan, ops.StageOneTables, "embed_shots")
+        ops._device_arg(frames_u8, "frames", "embed_shots", (torch.uint8,), shape=(plan.frames, None, None, 3),
+                        device=plan.device)
+        dev, (h, w) = frames_u8.device, frames_u8.shape[1:3]
+        sizes = [s for s in ((224, 224), (299, 299)) if s != (h, w)]
+        with torch.no_grad():
+            feats = torch.empty((plan.nsamples, 4096), dtype=torch.float32, device=dev)
+            for i, (gsz, lo, hi) in enumerate(plan.passes):
+                index = plan.pass_frame_index_t[lo:hi]
+                resized = dict(zip(sizes, ops.resize_gather(frames_u8, index, hi - lo, sizes)))
+                if len(sizes) < 2:
+                    resized[(h, w)] = ops.gather_rows(frames_u8, index, plan.pass_counts_t[i:i + 1])
+                groups = torch.arange(0, hi - lo + 1, gsz, dtype=torch.int64)
+                self._resnet_runner.forward(resized[(224, 224)], groups, out=feats[lo:hi, :2048])
+                self._inception_runner.forward(resized[(299, 299)], out=feats[lo:hi, 2048:])
+            out = torch.empty((plan.nshots, 4096), dtype=torch.float32, device=dev)
+            ops.segment_mean_perm(feats[:, :2048], plan.row_of_sample_t, plan.samples, out[:, :2048])
+            ops.segment_mean_perm(feats[:, 2048:], plan.row_of_sample_t, plan.samples, out[:, 2048:])
+        # the clustered BatchNorm launches of this call: fail loudly instead of returning features normalised with
+        # incomplete statistics (FrameScoringPipeline.score).  Reads one counter back
+        bad = ops.cluster_exchange_errors(dev)
+        if bad:
+            raise RuntimeError(f"clustered BatchNorm: {bad} wave(s) gave up waiting for a partner tile's statistics")
+        return out
+
     def _preprocess_frame(self, frame):
         """extractors.py:126-140 -> Tensor [1,3,224,224] (resize, (x-mean)/std, no /255)."""
         f = self._to_device_u8([_as_bgr_u8(frame)])
@@ -279,6 +312,49 @@ class AVProcessor:
         if batch_audio:
             return np.array(visual), self.audio_extractor.forward_shots(waveform, bounds)
         return np.array(visual), np.array(audio)
+
+    def process_decoded_batch(self, frames_u8, video_offsets, waveforms, fps, shots=None, chunk_frames=4096):
+        """process_decoded(..., batch_audio=True) for a ragged batch of V videos: a list of V (visual, audio) pairs, pair v
+        what process_decoded(frames of video v, waveforms[v], fps of video v, shots of video v, batch_audio=True) returns,
+        in shapes and dtypes too (np.array([]) twice for a video without shots, a zero visual row for an empty shot).
+        ``frames_u8``: uint8 [N,h,w,3], the videos concatenated - a device tensor, or a numpy array uploaded once;
+        ``video_offsets``: the host frame offsets [V + 1]; ``fps``: one number or one per video; ``shots``: one host
+        [(start, end)] list per video, a features.shots.ShotBatchResult, or None to run detect_shots_batch.  The visual
+        rows of all shots come from ONE VisualFeatureExtractor.embed_shots call (passes of at most ``chunk_frames``
+        frames) and one download, the audio rows from ONE AudioFeatureExtractor.forward_shots_batch call."""
+        from .shots import ShotBatchResult, detect_shots_batch
+        if isinstance(frames_u8, np.ndarray):
+            frames_u8 = torch.from_numpy(np.ascontiguousarray(frames_u8)).to(_device())
+        if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
+            raise ValueError("process_decoded_batch: frames must be a numpy array or a device tensor")
+        frames_u8 = frames_u8.contiguous()
+        if shots is None:
+            shots = detect_shots_batch(frames_u8, video_offsets)
+        if isinstance(shots, ShotBatchResult):
+            plan = ops.StageOneTables.from_result(shots, chunk_frames)
+            if not np.array_equal(plan.offsets, np.asarray(video_offsets, dtype=np.int64).reshape(-1)):
+                raise ValueError("process_decoded_batch: the shots were detected for other video offsets")
+        else:
+            plan = ops.StageOneTables(video_offsets, shots, chunk_frames, frames_u8.device)
+        nv = plan.nvideos
+        fps = [fps] * nv if np.isscalar(fps) else list(fps)
+        if len(fps) != nv or len(waveforms) != nv:
+            raise ValueError(f"process_decoded_batch: {nv} videos, {len(waveforms)} waveforms, {len(fps)} fps values")
+        visual = self.visual_extractor.embed_shots(frames_u8, plan).cpu().numpy()
+        off = plan.shot_offsets
+        bounds = [[(int(start / f * self.sr), int(end / f * self.sr)) for start, end in plan.shots[off[v]:off[v + 1]].tolist()]
+                  for v, f in enumerate(fps)]
+        audio = self.audio_extractor.forward_shots_batch(waveforms, bounds)
+        pairs = []
+        for v in range(nv):
+            if off[v] == off[v + 1]:
+                pairs.append((np.array([]), np.array([])))     # np.array of an empty list of rows, as process_decoded
+                continue
+            rows = audio[off[v]:off[v + 1]]
+            if rows.dtype != np.float32 and all(len(np.asarray(waveforms[v])[a:b]) < 1 for a, b in bounds[v]):
+                rows = rows.astype(np.float32)      # strict mode: forward's float32 zeros where every clip is empty
+            pairs.append((visual[off[v]:off[v + 1]], rows))
+        return pairs
 
     def process_video(self, video_path):
         """extractors.py:304-362: (np[S,4096], np[S,296]) for the shots of one video file.  Decode and audio demux

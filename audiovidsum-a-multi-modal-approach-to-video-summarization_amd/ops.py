@@ -13,7 +13,7 @@ from ._abi import (ACT_NONE, ACT_RELU, AVS_BF16, AVS_F16X2, AVS_F32, AVS_F32_SPL
                    lib)
 from .ragged import (EVAL_CHUNK, EVAL_MAX_T, EVAL_TILE, FUSION_MAX_N, FUSION_MID_L, FUSION_SMALL_L,  # noqa: F401
                      SHOT_INTERVAL, SHOT_MAX_FRAMES, SHOT_MICRO_BATCH, SUMMARY_MAX_CAPACITY, SUMMARY_MAX_ROWS, EvalTables,
-                     FusionTables, RaggedOffsets, SeqTable, ShotTables, SummaryTables)
+                     FusionTables, RaggedOffsets, SeqTable, ShotTables, StageOneTables, SummaryTables)
 
 __all__ = [
     "ACT_NONE", "ACT_RELU", "linear", "gemm_nt_batched", "conv2d", "conv2d_raw", "conv2d_split", "conv_bnlocal_tile_rows", "conv_bncluster_ok", "conv_bnstats_ok", "cluster_exchange_errors", "lstm_split_errors", "conv1x1_bn", "conv1x1_gram_bn", "bn_gram_affine", "gram_supported", "frames_normalize", "pull_copy", "stem_conv_bn_pool", "stem_h2_operands", "stem_conv_pool_h2", "resize_bilinear",
@@ -23,6 +23,7 @@ __all__ = [
     "SeqTable", "seq_shift_rows", "seq_mse",
     "ShotTables", "hsv_frame_diff_batch", "shot_cuts_batch", "shot_tables", "gather_rows",
     "SummaryTables", "shot_value_sums", "knapsack_batch", "mask_overlap_counts",
+    "StageOneTables", "resize_gather", "segment_mean_perm",
 ]
 
 
@@ -1759,6 +1760,72 @@ def gather_rows(src, index, count, out=None):
         _device_arg(out, "out", "gather_rows", (src.dtype,), shape=(cap,) + row_shape, device=src.device)
     check(lib().avs_gather_rows_u8(_p(src), src.shape[0], row_bytes, _p(index), _p(count), cap, _p(out), _stream()),
           "avs_gather_rows_u8")
+    return out
+
+
+# --------------------------------------------------------------------------- batched stage-1 extraction
+def resize_gather(frames_u8, index, count, sizes, outs=None):
+    """[cv2-bilinear resize of frames_u8[index[i]] to (dh, dw), i < count] for each (dh, dw) of ``sizes`` - one size or
+    two - in ONE launch: the frames are read where they lie, no dense copy of the gathered frames is made.  ``frames_u8``
+    uint8 [R, h, w, 3] contiguous device tensor; ``index`` int64 device vector of at least ``count`` rows of it; ``count``
+    a host integer.  Returns a list of uint8 [count, dh, dw, 3] tensors, ``outs`` where given.  Byte for byte
+    resize_bilinear(frames_u8.index_select(0, index[:count]), dh, dw); a row whose index lies outside frames_u8 is
+    skipped (left as it was)."""
+    _device_arg(frames_u8, "frames", "resize_gather", (torch.uint8,), shape=(None, None, None, 3))
+    _device_arg(index, "index", "resize_gather", (torch.int64,), ndim=1, device=frames_u8.device)
+    count = int(count)
+    if not 0 <= count <= index.numel():
+        raise ValueError(f"resize_gather: count {count} outside 0 .. {index.numel()}, the entries of index")
+    sizes = [(int(dh), int(dw)) for dh, dw in sizes]
+    if len(sizes) not in (1, 2) or any(dh < 1 or dw < 1 for dh, dw in sizes):
+        raise ValueError(f"resize_gather: sizes must be one or two (dh, dw) of positive extents, got {sizes}")
+    r, h, w, _ = frames_u8.shape
+    if h < 1 or w < 1:
+        raise ValueError(f"resize_gather: frames of shape {list(frames_u8.shape)} are empty")
+    if outs is None:
+        outs = [torch.empty((count, dh, dw, 3), dtype=torch.uint8, device=frames_u8.device) for dh, dw in sizes]
+    elif len(outs) != len(sizes):
+        raise ValueError(f"resize_gather: {len(outs)} outs for {len(sizes)} sizes")
+    for k, ((dh, dw), out) in enumerate(zip(sizes, outs)):
+        _device_arg(out, f"outs[{k}]", "resize_gather", (torch.uint8,), shape=(count, dh, dw, 3), device=frames_u8.device)
+    (dh0, dw0), (dh1, dw1) = sizes[0], sizes[1] if len(sizes) == 2 else (0, 0)
+    check(lib().avs_resize_bilinear_gather2_u8(_p(frames_u8), r, h, w, _p(index), count, _p(outs[0]), dh0, dw0,
+                                               _p(outs[1]) if len(sizes) == 2 else None, dh1, dw1, _stream()),
+          "avs_resize_bilinear_gather2_u8")
+    return list(outs)
+
+
+def segment_mean_perm(x2d, perm, seg, out=None):
+    """out[s, :] = mean over k of x2d[perm[seg[s] + k], :], k ascending: bit for bit segment_mean(x2d.index_select(0,
+    perm), seg) without the permuted copy.  ``x2d`` fp32 [R, d] device tensor with unit column stride (a column slice is
+    fine); ``perm`` int64 device vector of rows of x2d; ``seg`` the segment offsets [S + 1] into perm: an int64 device
+    vector, or a RaggedOffsets uploaded to the device, whose span is then checked against perm (a device vector is
+    trusted: entries outside perm, like rows outside x2d, are passed over).  ``out`` fp32 [S, d] with unit column stride
+    (allocated when None).  An empty segment gives a row of zeros."""
+    _device_arg(x2d, "x", "segment_mean_perm", (torch.float32,), ndim=2, contiguous=False)
+    if x2d.shape[1] < 1 or (x2d.shape[1] > 1 and x2d.stride(1) != 1) or (x2d.shape[0] > 1 and x2d.stride(0) < x2d.shape[1]):
+        raise ValueError(f"segment_mean_perm: x must have unit column stride and at least one column, got shape "
+                         f"{list(x2d.shape)} with strides {list(x2d.stride())}")
+    _device_arg(perm, "perm", "segment_mean_perm", (torch.int64,), ndim=1, device=x2d.device)
+    if isinstance(seg, RaggedOffsets):
+        if seg.device != x2d.device:
+            raise ValueError(f"segment_mean_perm: seg is on {seg.device}, the other arguments on {x2d.device}")
+        if seg.total != perm.numel() or seg.offsets[0] != 0:
+            raise ValueError(f"segment_mean_perm: seg spans {int(seg.offsets[0])} .. {seg.total}, perm has {perm.numel()} "
+                             "entries")
+        seg = seg.offsets_t
+    _device_arg(seg, "seg", "segment_mean_perm", (torch.int64,), ndim=1, device=x2d.device)
+    if seg.numel() < 1:
+        raise ValueError("segment_mean_perm: seg must hold S + 1 entries")
+    nseg, d = seg.numel() - 1, x2d.shape[1]
+    if out is None:
+        out = torch.empty((nseg, d), dtype=torch.float32, device=x2d.device)
+    else:
+        _device_arg(out, "out", "segment_mean_perm", (torch.float32,), shape=(nseg, d), device=x2d.device, contiguous=False)
+        if (d > 1 and out.stride(1) != 1) or (nseg > 1 and out.stride(0) < d):
+            raise ValueError(f"segment_mean_perm: out must have unit column stride, got strides {list(out.stride())}")
+    check(lib().avs_segment_mean_perm_f32(_p(x2d), max(x2d.stride(0), d), x2d.shape[0], d, _p(perm), perm.numel(), _p(seg), nseg,
+                                          _p(out), max(out.stride(0), d), _stream()), "avs_segment_mean_perm_f32")
     return out
 
 

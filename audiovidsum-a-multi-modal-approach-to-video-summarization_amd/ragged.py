@@ -1,6 +1,6 @@
 """Host plans of the ragged-batch layers: row offsets validated on the host and uploaded once (RaggedOffsets and the
-four tables built on it - EvalTables, SeqTable, ShotTables, SummaryTables) and the pair tables of the batched fusion
-(FusionTables).
+five tables built on it - EvalTables, SeqTable, ShotTables, StageOneTables, SummaryTables) and the pair tables of the
+batched fusion (FusionTables).
 Pure host code on numpy and torch: nothing here touches the kernel library, so the plans can be built and checked with
 ``device="cpu"`` where there is no GPU.  ops.py re-exports every name and holds the launch wrappers that take them."""
 import numpy as np
@@ -162,6 +162,81 @@ class ShotTables(RaggedOffsets):
         self.group_cap = int((thirds // SHOT_MICRO_BATCH + slots + 1).sum())
         self.packed_sizes = (4, 3 * (self.nvideos + 1), 2 * self.shot_cap, self.shot_cap + 1, self.group_cap + 1)
         self.cut_off_t, = _upload(self.device, self.cut_off)
+
+
+class StageOneTables(RaggedOffsets):
+    """The host plan of the batched stage-1 extraction (VisualFeatureExtractor.embed_shots), built once from the host
+    frame offsets [V + 1] of the videos in the concatenated frames and one ``[(start, end)]`` shot list per video - any
+    list AVProcessor.process_decoded takes: shots may overlap, ``end`` past the video is clipped to its length,
+    ``start >= end`` is an empty shot, a video may have none.  from_result builds it from a detect_shots_batch result.
+
+    Host side (numpy int64): ``offsets``, ``lengths``, ``nvideos``, ``frames``; ``shot_offsets`` [V + 1], ``shots``
+    [S, 2] (video-relative, as given), ``shot_video`` [S], ``nshots``; ``sample_offsets`` [S + 1], ``sample_index`` [F]
+    (rows of the concatenated frames, shot by shot: base[v] + sample_shot_indices(start, min(end, n_v))), ``nsamples``;
+    ``group_offsets`` [G + 1]: per shot ceil(c / 4) BatchNorm groups of 4 with a shorter tail, never across two shots
+    (for shots that tile the videos: the tables of features.shots.shot_tables_host).  The uniform sets: for each group
+    size r of 4, 3, 2, 1 that occurs the sample positions of all frames in groups of r frames, in shot order, one set
+    after another, are ``pass_order`` [F] (pass row -> sample position); ``row_of_sample`` [F] is its inverse,
+    ``pass_frame_index`` = sample_index[pass_order] the source frame of every pass row, and ``passes`` the list of
+    (group size, row_lo, row_hi) covering 0 .. F in order: each holds whole groups of ONE size and at most
+    ``chunk_frames`` frames.  ``samples``: sample_offsets as the RaggedOffsets ops.segment_mean_perm checks.
+    Device side: ``offsets_t``, ``pass_frame_index_t``, ``row_of_sample_t``, ``sample_offsets_t`` and ``pass_counts_t``
+    [len(passes)] (hi - lo: the device row count ops.gather_rows reads), each uploaded once.  ``device="cpu"`` keeps
+    everything on the host (the builder can be checked without a GPU).  Refused, each with a ValueError: what ShotTables
+    refuses about the offsets (more than 2^24 frames among it), a list count other than V, a negative start,
+    chunk_frames < 4."""
+
+    def __init__(self, offsets_host, shots_per_video, chunk_frames=4096, device=None):
+        super().__init__(offsets_host, "StageOneTables", device=device, max_total=1 << 24, total_inclusive=True)
+        if int(chunk_frames) < SHOT_MICRO_BATCH:
+            raise ValueError(f"StageOneTables: chunk_frames must be >= {SHOT_MICRO_BATCH}, got {chunk_frames}")
+        shots_per_video = list(shots_per_video)
+        if len(shots_per_video) != self.count:
+            raise ValueError(f"StageOneTables: {len(shots_per_video)} shot lists for {self.count} videos")
+        self.nvideos, self.frames, self.chunk_frames = self.count, self.total, int(chunk_frames)
+        per_video = [np.asarray(list(s), dtype=np.int64).reshape(-1, 2) for s in shots_per_video]
+        self.shot_offsets = exclusive_offsets([s.shape[0] for s in per_video])
+        self.shots = np.concatenate(per_video).reshape(-1, 2)
+        self.nshots = self.shots.shape[0]
+        self.shot_video = np.repeat(np.arange(self.nvideos, dtype=np.int64), np.diff(self.shot_offsets))
+        start, end = self.shots[:, 0], np.minimum(self.shots[:, 1], self.lengths[self.shot_video])
+        if (start < 0).any():
+            raise ValueError("StageOneTables: a shot starts at a negative frame")
+        first = -(-start // SHOT_INTERVAL)                                     # ceil(start / 3)
+        count = np.clip(-(-end // SHOT_INTERVAL) - first, 0, SHOT_MAX_FRAMES)   # (start >= end: no multiple of 3 between)
+        self.samples = RaggedOffsets(exclusive_offsets(count), "StageOneTables: sample_offsets", device=self.device,
+                                     allow_empty=True, min_length=0)
+        self.sample_offsets, self.nsamples = self.samples.offsets, self.samples.total
+        shot_of, k = segment_tiles(count)
+        self.sample_index = self.offsets[self.shot_video[shot_of]] + SHOT_INTERVAL * (first[shot_of] + k)
+        # group g of a shot holds its samples 4 g .. min(4 g + 4, c): the size of the group a sample lies in
+        groups = -(-count // SHOT_MICRO_BATCH)
+        gshot, g = segment_tiles(groups)
+        self.group_offsets = np.concatenate([self.sample_offsets[:-1][gshot] + SHOT_MICRO_BATCH * g,
+                                             [self.nsamples]]).astype(np.int64)
+        size_of = np.minimum(SHOT_MICRO_BATCH, count[shot_of] - k // SHOT_MICRO_BATCH * SHOT_MICRO_BATCH)
+        order, self.passes = [], []
+        for r in range(SHOT_MICRO_BATCH, 0, -1):
+            members = np.flatnonzero(size_of == r)
+            row0, step = sum(o.size for o in order), self.chunk_frames // r * r
+            self.passes += [(r, row0 + lo, row0 + min(lo + step, members.size)) for lo in range(0, members.size, step)]
+            order.append(members)
+        self.pass_order = np.concatenate(order).astype(np.int64)
+        self.row_of_sample = np.empty(self.nsamples, dtype=np.int64)
+        self.row_of_sample[self.pass_order] = np.arange(self.nsamples, dtype=np.int64)
+        self.pass_frame_index = self.sample_index[self.pass_order]
+        self.pass_counts = np.array([hi - lo for _, lo, hi in self.passes], dtype=np.int64)
+        self.sample_offsets_t = self.samples.offsets_t
+        self.pass_frame_index_t, self.row_of_sample_t, self.pass_counts_t = _upload(
+            self.device, self.pass_frame_index, self.row_of_sample, self.pass_counts)
+
+    @classmethod
+    def from_result(cls, result, chunk_frames=4096):
+        """The plan of a features.shots.ShotBatchResult (detect_shots_batch): its videos and the shots of its
+        host_tables() - the result's one download - on the result's device."""
+        t, plan = result.host_tables(), result.plan
+        shots, off = t["shots"], t["shot_offsets"]
+        return cls(plan.offsets, [shots[off[v]:off[v + 1]] for v in range(plan.nvideos)], chunk_frames, plan.device)
 
 
 class SummaryTables(RaggedOffsets):

@@ -893,6 +893,28 @@ int avs_knapsack_batch_f64(const int64_t* d_sums, int nrows, int64_t n, const in
 int avs_mask_overlap_counts(const uint8_t* d_pred_mask, const uint8_t* d_user_masks, int64_t ld_user, int nusers,
                             int64_t n, const int64_t* d_offsets, int nvideos, int64_t* d_counts, avs_stream_t stream);
 
+/* ---- batched stage-1 extraction: the glue around the two CNN trunks (features/extractors.py:344-362 for every shot of
+ * a ragged batch; csrc/stage1_batch.hip) ------------------------------------------------------------------------------
+ * d_dst0[i] = cv2.resize(d_src[d_index[i]], (dw0, dh0), INTER_LINEAR) for i < count and, where d_dst1 is not null, the
+ * same for d_dst1 at (dw1, dh1), in ONE launch: d_src uint8 [src_rows, sh, sw, 3] is read where it lies (no dense copy
+ * of the gathered frames), d_index int64 [>= count] on the device, count a host integer, d_dst* uint8 [count, dh, dw, 3].
+ * The bytes are those of avs_resize_bilinear_u8 on the gathered frames.  An index outside [0, src_rows) is skipped: its
+ * destination rows are left as they were.  Any alignment of the three bases is taken.  One workgroup resizes a band of
+ * 8 output rows (fewer while the source rows of a band exceed 64 KiB of LDS); AVS_E_UNSUPPORTED when two source rows and
+ * one output row do not fit, or for more than 65535 source columns or output rows.  count < 2^31.                      */
+int avs_resize_bilinear_gather2_u8(const uint8_t* d_src, int64_t src_rows, int sh, int sw, const int64_t* d_index,
+                                   int64_t count, uint8_t* d_dst0, int dh0, int dw0, uint8_t* d_dst1, int dh1, int dw1,
+                                   avs_stream_t stream);
+
+/* d_out[s, 0:d] = mean over k of d_x[d_perm[d_seg[s] + k], 0:d], k ascending, for s < nseg: avs_segment_mean_f32 reading
+ * its rows through a permutation, with the same additions in the same order (the bytes of avs_segment_mean_f32 on the
+ * permuted rows).  d_x fp32 [x_rows, >= d] with row stride ldx, d_perm int64 [perm_len], d_seg int64 [nseg + 1] positions
+ * in d_perm, d_out fp32 with row stride ldo (a column slice of a wider matrix is fine).  An empty segment gives a row of
+ * zeros.  A position outside d_perm, or a row outside d_x, is passed over.                                              */
+int avs_segment_mean_perm_f32(const float* d_x, int64_t ldx, int64_t x_rows, int d, const int64_t* d_perm,
+                              int64_t perm_len, const int64_t* d_seg, int nseg, float* d_out, int64_t ldo,
+                              avs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
