@@ -20,6 +20,10 @@
 // Groups larger than a tile run clustered (p.cluster > 1: one tile per 193..224-row member of the group, the tiles exchange
 // their statistics), or PACKED (p.packed: tiles of 224 consecutive rows whatever the group size - a multiple of 112 rows - so
 // no tile runs a 32-row block for 4 live rows; a tile then holds rows of one or of two groups, the boundary at its row 112).
+//
+// The main loop exists in two matrix-instruction shapes (template parameter SHAPE, chosen per instance at compile time from
+// the measurements in profiles/r07_*): 32 = the loop described above; 16 = v_mfma_f32_16x16x32_f16 on the same tile per
+// wave, two reduction steps paired - see the comment in front of the kernel.
 #include "avs_internal.h"
 #include "igemm_params.h"
 #include <type_traits>
@@ -45,10 +49,82 @@ template <int... I>
 __device__ __forceinline__ void read_blocks(uint4 (&f)[L_MT], unsigned addr, std::integer_sequence<int, I...>) {
   ((f[I] = lds_read_b128_at<I * 32 * 64>(addr)), ...);
 }
+
+// ---- SHAPE 16 (v_mfma_f32_16x16x32_f16): fourteen 16-row blocks, two 16-column blocks per wave ----
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int L_MT16 = L_ROWS / 16;         // 16-row blocks per wave
+template <int... I>
+__device__ __forceinline__ void read_blocks16(uint4 (&f)[L_MT16], unsigned addr, std::integer_sequence<int, I...>) {
+  ((f[I] = lds_read_b128_at<I * 16 * 64>(addr)), ...);
+}
+// Seven blocks' ds_read_b128 on ONE half of the wave (UPPER: lanes 32 .. 63, else lanes 0 .. 31); the other half of every
+// register keeps what it holds.  All 64 lanes are active around the main loop, so EXEC is restored to all ones.
+template <int B0, bool UPPER>
+__device__ __forceinline__ void read_half7(uint4 (&f)[L_MT16], unsigned addr) {
+  u32x4 r0 = __builtin_bit_cast(u32x4, f[B0 + 0]), r1 = __builtin_bit_cast(u32x4, f[B0 + 1]),
+        r2 = __builtin_bit_cast(u32x4, f[B0 + 2]), r3 = __builtin_bit_cast(u32x4, f[B0 + 3]),
+        r4 = __builtin_bit_cast(u32x4, f[B0 + 4]), r5 = __builtin_bit_cast(u32x4, f[B0 + 5]),
+        r6 = __builtin_bit_cast(u32x4, f[B0 + 6]);
+  if constexpr (UPPER)
+    asm volatile(
+        "s_mov_b32 exec_lo, 0\n\t"
+        "ds_read_b128 %0, %7 offset:%8\n\tds_read_b128 %1, %7 offset:%9\n\tds_read_b128 %2, %7 offset:%10\n\t"
+        "ds_read_b128 %3, %7 offset:%11\n\tds_read_b128 %4, %7 offset:%12\n\tds_read_b128 %5, %7 offset:%13\n\t"
+        "ds_read_b128 %6, %7 offset:%14\n\t"
+        "s_mov_b32 exec_lo, -1"
+        : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6)
+        : "v"(addr), "n"((B0 + 0) * 1024), "n"((B0 + 1) * 1024), "n"((B0 + 2) * 1024), "n"((B0 + 3) * 1024),
+          "n"((B0 + 4) * 1024), "n"((B0 + 5) * 1024), "n"((B0 + 6) * 1024));
+  else
+    asm volatile(
+        "s_mov_b32 exec_hi, 0\n\t"
+        "ds_read_b128 %0, %7 offset:%8\n\tds_read_b128 %1, %7 offset:%9\n\tds_read_b128 %2, %7 offset:%10\n\t"
+        "ds_read_b128 %3, %7 offset:%11\n\tds_read_b128 %4, %7 offset:%12\n\tds_read_b128 %5, %7 offset:%13\n\t"
+        "ds_read_b128 %6, %7 offset:%14\n\t"
+        "s_mov_b32 exec_hi, -1"
+        : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6)
+        : "v"(addr), "n"((B0 + 0) * 1024), "n"((B0 + 1) * 1024), "n"((B0 + 2) * 1024), "n"((B0 + 3) * 1024),
+          "n"((B0 + 4) * 1024), "n"((B0 + 5) * 1024), "n"((B0 + 6) * 1024));
+  f[B0 + 0] = __builtin_bit_cast(uint4, r0); f[B0 + 1] = __builtin_bit_cast(uint4, r1);
+  f[B0 + 2] = __builtin_bit_cast(uint4, r2); f[B0 + 3] = __builtin_bit_cast(uint4, r3);
+  f[B0 + 4] = __builtin_bit_cast(uint4, r4); f[B0 + 5] = __builtin_bit_cast(uint4, r5);
+  f[B0 + 6] = __builtin_bit_cast(uint4, r6);
+}
+// the wave's two B blocks (16 columns = 1024 bytes apart), lanes 32 .. 63 only
+__device__ __forceinline__ void read_upper2(uint4 (&f)[2], unsigned addr) {
+  u32x4 r0 = __builtin_bit_cast(u32x4, f[0]), r1 = __builtin_bit_cast(u32x4, f[1]);
+  asm volatile(
+      "s_mov_b32 exec_lo, 0\n\t"
+      "ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:1024\n\t"
+      "s_mov_b32 exec_lo, -1"
+      : "+v"(r0), "+v"(r1)
+      : "v"(addr));
+  f[0] = __builtin_bit_cast(uint4, r0);
+  f[1] = __builtin_bit_cast(uint4, r1);
+}
+// zeroes lanes 32 .. 63 of a fragment (the partner half of a pair that has no second step)
+__device__ __forceinline__ void zero_upper(uint4& f) {
+  asm volatile(
+      "s_mov_b32 exec_lo, 0\n\t"
+      "v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\tv_mov_b32 %3, 0\n\t"
+      "s_mov_b32 exec_lo, -1"
+      : "+v"(f.x), "+v"(f.y), "+v"(f.z), "+v"(f.w));
+}
 }  // namespace
 
-template <bool SPATIAL>
+// SHAPE: the matrix instruction of the main loop.  32 = v_mfma_f32_32x32x16_f16, 21 per step.  16 = v_mfma_f32_16x16x32_f16
+// on the same tile per wave (14 x 2 blocks of 16 x 16): an instruction reduces over 32 slots and a step carries 16
+// channels x three terms = 48, so steps are PAIRED.  Every step issues P = (hi + lo) . hi per block (A lane groups: hi 0-7,
+// hi 8-15, lo 0-7, lo 8-15 of the step; B: hi 0-7, hi 8-15 twice); every second step issues Q = hi . lo of BOTH steps (lanes
+// 0 .. 31: the even step's chunks, lanes 32 .. 63: the odd step's).  Q's operands are formed in place: lanes 0 .. 31 of the
+// even step's P fragment are its hi chunks already, at the odd step a half-wave read puts the odd step's hi chunks into lanes
+// 32 .. 63 of the same registers, and when Q has been issued a second half-wave read puts the odd step's lo chunks into lanes
+// 0 .. 31 - the registers then are the odd step's P fragment (lo | hi).  Nothing is read from a buffer after its own step.
+// A lane (i = lane & 15) reads row i ^ ((i >> 1) & 4) of a block (rows 8 .. 11 and 12 .. 15 trade places): with the image's
+// swizzle the chunk pairs (0, 2) and (1, 3) of one instruction then fall on sixteen different 16-byte slots per lane group.
+template <bool SPATIAL, int SHAPE>
 __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p) {
+  static_assert(SHAPE == 32 || SHAPE == 16, "SHAPE: 32 (v_mfma_f32_32x32x16_f16) or 16 (v_mfma_f32_16x16x32_f16)");
   __shared__ uint4 lds[3 * L_BUF];
 
   // XCD-aware, bijective block remap (as igemm_kernel): blocks that share an XCD take consecutive tiles
@@ -205,11 +281,41 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
 
   const int lr = lane & 31, lh = lane >> 5;
 
-  f32x16 acc[L_MT];
+  f32x16 acc[L_MT];             // SHAPE 32
+  f32x4 acc16[L_MT16][2];       // SHAPE 16: [16-row block][16-column block]
+  if constexpr (SHAPE == 32) {
 #pragma unroll
-  for (int i = 0; i < L_MT; ++i)
+    for (int i = 0; i < L_MT; ++i)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+      for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+  } else {
+#pragma unroll
+    for (int i = 0; i < L_MT16; ++i)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc16[i][cb][e] = 0.f;
+  }
+  // SHAPE 16: lane (li, lg) feeds slots 8 * lg .. + 7 of A row rho(li) / B column li of a block and holds, of the result,
+  // column li, rows 4 * rgp + 0 .. 3 (the row groups 2 and 3 trade places as the A rows do)
+  const int li = lane & 15, lg = lane >> 4;
+  const int rho = li ^ ((li >> 1) & 4);
+  const int rgp = lg ^ (lg >> 1);
+  // byte offsets inside a buffer (block b of A: + b * 1024, the second B block: + 1024; the swizzle term depends on the
+  // row's low four bits only).  Even step: A chunks [0, 2, 1, 3][lg].  Odd step: [1, 3, 0, 2][lg] - the upper half read
+  // first, the lower half when Q is issued.  B: P reads [0, 2, 0, 2][lg], Q reads [1, 3][lg & 1] (lanes 0 .. 31 from the even
+  // step's buffer, lanes 32 .. 63 from the odd step's).
+  unsigned fa16_even, fa16_odd, fb16_p, fb16_q;
+  {
+    const int hk = 2 * (lg & 1);
+    const int sw = (rho >> 2) & (L_CPRR - 1);
+    fa16_even = (unsigned)(rho * L_CPRR + ((hk + (lg >> 1)) ^ sw)) * 16u;
+    fa16_odd = (unsigned)(rho * L_CPRR + ((hk + 1 - (lg >> 1)) ^ sw)) * 16u;
+    const int brow = wave * 32 + li;
+    const int swb = (brow >> 2) & (L_CPRR - 1);
+    fb16_p = (unsigned)((L_ROWS + brow) * L_CPRR + (hk ^ swb)) * 16u;
+    fb16_q = (unsigned)((L_ROWS + brow) * L_CPRR + ((hk + 1) ^ swb)) * 16u;
+  }
 
   // per-lane fragment byte offsets inside a buffer: a row's chunks alternate hi8 | lo8; this lane half feeds elements
   // 8 * lh .. + 7 of the step: hi = chunk 2 * lh, lo = chunk 2 * lh + 1.  Block mt of A is mt * 32 rows further: an
@@ -247,65 +353,180 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
       rlo[mt % DEPTH][it] = rp[1];
     }
   };
+  // (SHAPE 16 holds eight more fragment registers through the loop and keeps two blocks' rows in flight there, not three)
   if (p.residual) {
     res_fetch(std::integral_constant<int, 0>{});
     res_fetch(std::integral_constant<int, 1>{});
-    res_fetch(std::integral_constant<int, 2>{});
+    if constexpr (SHAPE == 32) res_fetch(std::integral_constant<int, 2>{});
   }
 
   const int steps = p.K / L_STEP;
   stage(0);
   if (steps > 1) stage(1);
   int cur = 0;  // buffer holding step s
-  for (int s = 0; s < steps; ++s) {
-    if (s + 1 < steps) {
-      if (extra)
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if constexpr (SHAPE == 32) {
+    for (int s = 0; s < steps; ++s) {
+      if (s + 1 < steps) {
+        if (extra)
+          asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        else
+          asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      __builtin_amdgcn_s_barrier();
+      const unsigned bbase = lds_base + (unsigned)cur * (L_BUF * 16u);
+      uint4 fah[L_MT], fal[L_MT], fbh, fbl;
+      fbh = avs_lds_read_b128(bbase + fb_off[0]);
+      read_blocks(fah, bbase + fa_off[0], std::make_integer_sequence<int, L_MT>{});
+      fbl = avs_lds_read_b128(bbase + fb_off[1]);
+      read_blocks(fal, bbase + fa_off[1], std::make_integer_sequence<int, L_MT>{});
+      // the DMA of step s+2 is issued while the fragment reads are in flight
+      if (s + 2 < steps) stage(cur == 0 ? 2 : cur - 1);  // (s+2) % 3 == (cur + 2) % 3
+      // hi*hi starts as soon as the hi fragments have landed (LDS reads return in order); every fragment passes through an
+      // empty asm after the wait that covers it, so no use of it can be scheduled ahead of that wait
+      asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(1 + L_MT) : "memory");
+      avs_pin(fbh);
+  #pragma unroll
+      for (int mt = 0; mt < L_MT; ++mt) avs_pin(fah[mt]);
+      __builtin_amdgcn_sched_barrier(0);
+  #pragma unroll
+      for (int mt = 0; mt < L_MT; ++mt)
+        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(avs_f16x8, fah[mt]),
+                                                         __builtin_bit_cast(avs_f16x8, fbh), acc[mt], 0, 0, 0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      avs_pin(fbl);
+  #pragma unroll
+      for (int mt = 0; mt < L_MT; ++mt) avs_pin(fal[mt]);
+      __builtin_amdgcn_sched_barrier(0);
+  #pragma unroll
+      for (int mt = 0; mt < L_MT; ++mt) {
+        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(avs_f16x8, fal[mt]),
+                                                         __builtin_bit_cast(avs_f16x8, fbh), acc[mt], 0, 0, 0);
+        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(avs_f16x8, fah[mt]),
+                                                         __builtin_bit_cast(avs_f16x8, fbl), acc[mt], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      cur = cur == 2 ? 0 : cur + 1;
     }
-    __builtin_amdgcn_s_barrier();
-    const unsigned bbase = lds_base + (unsigned)cur * (L_BUF * 16u);
-    uint4 fah[L_MT], fal[L_MT], fbh, fbl;
-    fbh = avs_lds_read_b128(bbase + fb_off[0]);
-    read_blocks(fah, bbase + fa_off[0], std::make_integer_sequence<int, L_MT>{});
-    fbl = avs_lds_read_b128(bbase + fb_off[1]);
-    read_blocks(fal, bbase + fa_off[1], std::make_integer_sequence<int, L_MT>{});
-    // the DMA of step s+2 is issued while the fragment reads are in flight
-    if (s + 2 < steps) stage(cur == 0 ? 2 : cur - 1);  // (s+2) % 3 == (cur + 2) % 3
-    // hi*hi starts as soon as the hi fragments have landed (LDS reads return in order); every fragment passes through an
-    // empty asm after the wait that covers it, so no use of it can be scheduled ahead of that wait
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(1 + L_MT) : "memory");
-    avs_pin(fbh);
+  } else {
+    // the same ring, barriers, DMA position and vmcnt waits; two steps per trip.  LDS reads return in order: every wait
+    // below names how many of the reads issued so far may still be in flight.
+    auto step_wait = [&](int s) {
+      if (s + 1 < steps) {
+        if (extra)
+          asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        else
+          asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      __builtin_amdgcn_s_barrier();
+    };
+    auto mfma_blocks = [&](auto first, const uint4 (&a)[L_MT16], const uint4 (&b)[2]) {
+      constexpr int b0 = decltype(first)::value;
 #pragma unroll
-    for (int mt = 0; mt < L_MT; ++mt) avs_pin(fah[mt]);
-    __builtin_amdgcn_sched_barrier(0);
+      for (int mt = b0; mt < b0 + 7; ++mt)
 #pragma unroll
-    for (int mt = 0; mt < L_MT; ++mt)
-      acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(avs_f16x8, fah[mt]),
-                                                       __builtin_bit_cast(avs_f16x8, fbh), acc[mt], 0, 0, 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    avs_pin(fbl);
+        for (int cb = 0; cb < 2; ++cb)
+          acc16[mt][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(avs_f16x8, a[mt]),
+                                                                 __builtin_bit_cast(avs_f16x8, b[cb]), acc16[mt][cb], 0, 0, 0);
+    };
+    auto pin7 = [&](auto first, uint4 (&a)[L_MT16]) {
+      constexpr int b0 = decltype(first)::value;
 #pragma unroll
-    for (int mt = 0; mt < L_MT; ++mt) avs_pin(fal[mt]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int mt = 0; mt < L_MT; ++mt) {
-      acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(avs_f16x8, fal[mt]),
-                                                       __builtin_bit_cast(avs_f16x8, fbh), acc[mt], 0, 0, 0);
-      acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(avs_f16x8, fah[mt]),
-                                                       __builtin_bit_cast(avs_f16x8, fbl), acc[mt], 0, 0, 0);
+      for (int mt = b0; mt < b0 + 7; ++mt) avs_pin(a[mt]);
+    };
+    constexpr std::integral_constant<int, 0> B0{};
+    constexpr std::integral_constant<int, 7> B7{};
+    uint4 fa[L_MT16], fbp[2], fbq[2];
+    auto even_step = [&](int s) {
+      // ---- even step: P from full-wave reads; fa's lanes 0 .. 31 and fbq's (the step's lo chunks) stay for Q ----
+      step_wait(s);
+      const unsigned bbase = lds_base + (unsigned)cur * (L_BUF * 16u);
+      fbp[0] = lds_read_b128_at<0>(bbase + fb16_p);
+      fbp[1] = lds_read_b128_at<1024>(bbase + fb16_p);
+      read_blocks16(fa, bbase + fa16_even, std::make_integer_sequence<int, L_MT16>{});
+      if (s + 2 < steps) stage(cur == 0 ? 2 : cur - 1);
+      asm volatile("s_waitcnt lgkmcnt(7)" ::: "memory");     // fbp, fa[0 .. 6]
+      avs_pin(fbp[0]);
+      avs_pin(fbp[1]);
+      pin7(B0, fa);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_blocks(B0, fa, fbp);
+      __builtin_amdgcn_sched_barrier(0);
+      fbq[0] = lds_read_b128_at<0>(bbase + fb16_q);          // (never more than 16 reads in flight, as in the SHAPE 32 loop)
+      fbq[1] = lds_read_b128_at<1024>(bbase + fb16_q);
+      asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");     // fa[7 .. 13]
+      pin7(B7, fa);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_blocks(B7, fa, fbp);
+      __builtin_amdgcn_sched_barrier(0);
+      cur = cur == 2 ? 0 : cur + 1;
+    };
+    auto odd_step = [&](int s) {
+      // ---- odd step: Q of the pair from upper-half reads, then P from lower-half reads into the same registers ----
+      step_wait(s);
+      const unsigned bbase = lds_base + (unsigned)cur * (L_BUF * 16u);
+      read_upper2(fbq, bbase + fb16_q);
+      read_half7<0, true>(fa, bbase + fa16_odd);
+      read_half7<7, true>(fa, bbase + fa16_odd);
+      if (s + 2 < steps) stage(cur == 0 ? 2 : cur - 1);
+      asm volatile("s_waitcnt lgkmcnt(7)" ::: "memory");     // fbq, fa[0 .. 6] (upper)
+      avs_pin(fbq[0]);
+      avs_pin(fbq[1]);
+      pin7(B0, fa);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_blocks(B0, fa, fbq);
+      __builtin_amdgcn_sched_barrier(0);
+      read_half7<0, false>(fa, bbase + fa16_odd);
+      fbp[0] = lds_read_b128_at<0>(bbase + fb16_p);
+      fbp[1] = lds_read_b128_at<1024>(bbase + fb16_p);
+      asm volatile("s_waitcnt lgkmcnt(9)" ::: "memory");     // fa[7 .. 13] (upper)
+      pin7(B7, fa);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_blocks(B7, fa, fbq);
+      __builtin_amdgcn_sched_barrier(0);
+      read_half7<7, false>(fa, bbase + fa16_odd);
+      asm volatile("s_waitcnt lgkmcnt(7)" ::: "memory");     // fbp, fa[0 .. 6] (lower)
+      avs_pin(fbp[0]);
+      avs_pin(fbp[1]);
+      pin7(B0, fa);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_blocks(B0, fa, fbp);
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      pin7(B7, fa);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_blocks(B7, fa, fbp);
+      __builtin_amdgcn_sched_barrier(0);
+      cur = cur == 2 ? 0 : cur + 1;
+    };
+    int s = 0;
+    for (; s + 1 < steps; s += 2) {
+      even_step(s);
+      odd_step(s + 1);
     }
-    __builtin_amdgcn_sched_barrier(0);
-    cur = cur == 2 ? 0 : cur + 1;
+    if (s < steps) {
+      even_step(s);
+      // an odd step count: the last Q carries one step, its partner half zeroed on both operands
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      zero_upper(fbq[0]);
+      zero_upper(fbq[1]);
+#pragma unroll
+      for (int mt = 0; mt < L_MT16; ++mt) zero_upper(fa[mt]);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_blocks(B0, fa, fbq);
+      mfma_blocks(B7, fa, fbq);
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
 
   // ---- epilogue: the group's BatchNorm from this wave's own registers, then 32 rows at a time through LDS ----
   // A lane holds column lr of its wave's 32, rows (e & 3) + 8 * (e >> 2) + 4 * lh of every block; rows >= used are
   // exact zeros (their operand rows were never fetched).
   if (p.residual) {
+    if constexpr (SHAPE == 16) res_fetch(std::integral_constant<int, 2>{});
     res_fetch(std::integral_constant<int, 3>{});
     res_fetch(std::integral_constant<int, 4>{});
     res_fetch(std::integral_constant<int, 5>{});
@@ -316,7 +537,59 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
   const int seg0 = p.packed ? (int)min((long long)used, (m0 / p.rows_per_group + 1ll) * p.rows_per_group - m0) : used;
   const bool shared = seg0 < used;   // (block-uniform) two segments, 112 rows each
   float mean, mean_b, s2, s2b = 0.f;
-  if (p.packed) {
+  if constexpr (SHAPE == 16) {
+    // A lane holds columns li and 16 + li of its wave's 32, rows 16 * mt + 4 * rgp + e of both: a column's sums are this
+    // lane's plus the three other row groups' (shuffles across 16 and 32 lanes), two centred rounds as above.  The packed
+    // boundary at row 112 lies between blocks 6 and 7.  The lane then keeps, as a SHAPE 32 lane does, the statistics of
+    // column lr = lane & 31 - those of its column block (lane >> 4) & 1 - so the exchanges below are the same bytes.
+    const int lim16 = used - 4 * rgp;   // block-local row offsets below this one exist
+    const float inv0 = p.packed ? 1.f / (float)seg0 : inv_n, inv1 = 1.f / (float)(shared ? used - seg0 : seg0);   // (uniform)
+    float mc[2], mbc[2], qc[2], qbc[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+      float s1 = 0.f, s1b = 0.f;
+#pragma unroll
+      for (int mt = 0; mt < L_MT16; ++mt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (mt < L_MT16 / 2)
+            s1 += acc16[mt][cb][e];
+          else
+            s1b += acc16[mt][cb][e];
+        }
+      s1 += __shfl_xor(s1, 16, 64);
+      s1b += __shfl_xor(s1b, 16, 64);
+      s1 += __shfl_xor(s1, 32, 64);
+      s1b += __shfl_xor(s1b, 32, 64);
+      mc[cb] = (shared ? s1 : s1 + s1b) * inv0;
+      mbc[cb] = shared ? s1b * inv1 : mc[cb];
+      float q = 0.f, qb = 0.f;
+#pragma unroll
+      for (int mt = 0; mt < L_MT16; ++mt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int roff = mt * 16 + e;
+          if (mt < L_MT16 / 2) {
+            const float d = acc16[mt][cb][e] - mc[cb];
+            q = roff < lim16 ? fmaf(d, d, q) : q;
+          } else {
+            const float d = acc16[mt][cb][e] - mbc[cb];
+            qb = roff < lim16 ? fmaf(d, d, qb) : qb;
+          }
+        }
+      q += __shfl_xor(q, 16, 64);
+      qb += __shfl_xor(qb, 16, 64);
+      q += __shfl_xor(q, 32, 64);
+      qb += __shfl_xor(qb, 32, 64);
+      qc[cb] = shared ? q : q + qb;
+      qbc[cb] = qb;
+    }
+    const bool c1 = (lg & 1) != 0;
+    mean = c1 ? mc[1] : mc[0];
+    mean_b = c1 ? mbc[1] : mbc[0];
+    s2 = c1 ? qc[1] : qc[0];
+    s2b = c1 ? qbc[1] : qbc[0];
+  } else if (p.packed) {
     float s1 = 0.f, s1b = 0.f;
 #pragma unroll
     for (int mt = 0; mt < L_MT; ++mt)
@@ -495,21 +768,49 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
     sc_b = p.gamma[col] / sqrtf(g_var_b + p.eps);
     sf_b = p.beta[col] - g_mean_b * sc_b;
   }
+  if constexpr (SHAPE == 32) {
 #pragma unroll
-  for (int mt = 0; mt < L_MT; ++mt)
+    for (int mt = 0; mt < L_MT; ++mt)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const bool first = mt < 3 || (mt == 3 && e < 8);   // (static per element)
-      acc[mt][e] = fmaf(acc[mt][e], first ? sc : sc_b, first ? sf : sf_b);
-    }
+      for (int e = 0; e < 16; ++e) {
+        const bool first = mt < 3 || (mt == 3 && e < 8);   // (static per element)
+        acc[mt][e] = fmaf(acc[mt][e], first ? sc : sc_b, first ? sf : sf_b);
+      }
+  } else {
+    // the pairs above are column lr's: one shuffle each gives the lane those of the other column block
+    const bool c1 = (lg & 1) != 0;
+    const float sc_o = __shfl_xor(sc, 16, 64), sf_o = __shfl_xor(sf, 16, 64);
+    const float scb_o = __shfl_xor(sc_b, 16, 64), sfb_o = __shfl_xor(sf_b, 16, 64);
+    const float sc2[2] = {c1 ? sc_o : sc, c1 ? sc : sc_o}, sf2[2] = {c1 ? sf_o : sf, c1 ? sf : sf_o};
+    const float scb2[2] = {c1 ? scb_o : sc_b, c1 ? sc_b : scb_o}, sfb2[2] = {c1 ? sfb_o : sf_b, c1 ? sf_b : sfb_o};
+#pragma unroll
+    for (int mt = 0; mt < L_MT16; ++mt)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool first = mt < L_MT16 / 2;   // (static per block)
+          acc16[mt][cb][e] = fmaf(acc16[mt][cb][e], first ? sc2[cb] : scb2[cb], first ? sf2[cb] : sfb2[cb]);
+        }
+  }
   const bool relu = p.act == AVS_ACT_RELU;
 
   __syncthreads();   // every wave has read its last fragments: the staging regions alias the operand buffers
   float* const wreg = reinterpret_cast<float*>(lds) + wave * (32 * L_P);
   auto emit = [&](auto blk) {
     constexpr int mt = decltype(blk)::value;
+    if constexpr (SHAPE == 32) {
 #pragma unroll
-    for (int e = 0; e < 16; ++e) wreg[((e & 3) + 8 * (e >> 2) + 4 * lh) * L_P + lr] = acc[mt][e];
+      for (int e = 0; e < 16; ++e) wreg[((e & 3) + 8 * (e >> 2) + 4 * lh) * L_P + lr] = acc[mt][e];
+    } else {
+      // two 16-row blocks make the 32 staged rows; lanes li and 16 + li of a store share a bank (two-way: free for stores)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) wreg[(h * 16 + 4 * rgp + e) * L_P + cb * 16 + li] = acc16[2 * mt + h][cb][e];
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     const long long row0 = (long long)m0 + mt * 32 + rl0;
@@ -574,9 +875,28 @@ bool igemm_h2_local224_ok(const IgemmParams& p, int dtype, long long lin_stride)
   return igemm_buffer_window_ok(p, lin_stride, 4, L_BN);
 }
 
+// The matrix instruction each instance ships with (profiles/r07_*: kept per instance as measured).  The study build can
+// force either shape for both instances: AVS_LOCAL224_MFMA = 16 or 32.
+constexpr int L_SHAPE_SPATIAL = 32;
+constexpr int L_SHAPE_POINT = 16;
+
 void igemm_h2_local224_launch(const IgemmParams& p, bool spatial, dim3 grid, hipStream_t stream) {
+#ifdef AVS_STUDY
+  const int forced = getenv("AVS_LOCAL224_MFMA") ? atoi(getenv("AVS_LOCAL224_MFMA")) : 0;
+  if (forced == 16 || forced == 32) {
+    if (spatial && forced == 16)
+      hipLaunchKernelGGL((igemm_h2_local224_kernel<true, 16>), grid, dim3(256), 0, stream, p);
+    else if (spatial)
+      hipLaunchKernelGGL((igemm_h2_local224_kernel<true, 32>), grid, dim3(256), 0, stream, p);
+    else if (forced == 16)
+      hipLaunchKernelGGL((igemm_h2_local224_kernel<false, 16>), grid, dim3(256), 0, stream, p);
+    else
+      hipLaunchKernelGGL((igemm_h2_local224_kernel<false, 32>), grid, dim3(256), 0, stream, p);
+    return;
+  }
+#endif
   if (spatial)
-    hipLaunchKernelGGL(igemm_h2_local224_kernel<true>, grid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((igemm_h2_local224_kernel<true, L_SHAPE_SPATIAL>), grid, dim3(256), 0, stream, p);
   else
-    hipLaunchKernelGGL(igemm_h2_local224_kernel<false>, grid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((igemm_h2_local224_kernel<false, L_SHAPE_POINT>), grid, dim3(256), 0, stream, p);
 }

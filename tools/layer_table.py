@@ -8,9 +8,11 @@ Per layer: time per pass, matrix rate (algorithmic FLOP / time), stream rate (bf
 time) and the time an ideal kernel would take: max(FLOP / 1.2 PFLOP/s, bytes / 5.5 TB/s) - 1.2 PF is what the LDS-DMA
 intake allows a 128x128-tile contraction here, 5.5 TB/s what a streaming kernel reaches on this chip.
 
-Usage: python tools/layer_table.py [--n 8192] [--gf 1] [--dtype bf16|f32split|f16x2] [--pack on|off|ab]"""
+Usage: python tools/layer_table.py [--n 8192] [--gf 1] [--dtype bf16|f32split|f16x2] [--pack on|off|ab] [--mfma 16|32|ab]"""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if any(a.startswith("--mfma") for a in sys.argv[1:]):
+    os.environ["AVS_STUDY_LIB"] = "1"  # the shape switch of the 224-row kernel lives in the study build only (make -C <pkg>/csrc study)
 import torch
 from avsum_amd import cnn, ops
 from avsum_amd.features.extractors import VisualFeatureExtractor
@@ -24,6 +26,9 @@ ap.add_argument("--set", action="append", default=[], help="runner attribute ove
 ap.add_argument("--p8", default="on", choices=["on", "off"], help="f16x2: AVS_F16P8 storage of the inner block outputs of layers 1-2")
 ap.add_argument("--pack", default="on", choices=["on", "off", "ab"],
                 help="f16x2, --gf 4: the packed clustered BatchNorm on / off, or ab: off, on, off in one run and a comparison of the cluster rows")
+ap.add_argument("--mfma", default="", choices=["", "16", "32", "ab"],
+                help="f16x2, study build: the 224-row kernel's matrix instruction forced to 16x16x32 / 32x32x16 (AVS_LOCAL224_MFMA), "
+                     "or ab: 32, 16, 32 in one run and a comparison of its rows per instance (3x3 / 1x1)")
 ap.add_argument("--short", type=int, default=0,
                 help="study build (AVS_STUDY_LIB=1): reductions of at most this many bytes per row take 64-byte steps (rule: 2048)")
 args = ap.parse_args()
@@ -199,7 +204,34 @@ def measure(label):
     return {k: (v[0], v[1]) for k, v in agg.items()}
 
 
-if args.pack != "ab":
+if args.mfma == "ab":
+    # shape 32, shape 16, shape 32 again in ONE process: the second shape-32 table gives the tool's repeatability per row.
+    # The rows of the 224-row kernel: the cluster and local forms of the 14x14 and 7x7 maps, per instance (3x3: spatial)
+    runner.pack_groups = args.pack != "off"
+    tabs = []
+    for label, shape in (("[mfma 32, 1st] ", "32"), ("[mfma 16] ", "16"), ("[mfma 32, 2nd] ", "32")):
+        os.environ["AVS_LOCAL224_MFMA"] = shape
+        tabs.append(measure(label))
+        print()
+    a1, s16, a2 = tabs
+    for inst, spatial in (("3x3 rows (SPATIAL = true)", True), ("1x1 rows (SPATIAL = false)", False)):
+        print(f"{inst:34s} {'shape 32':>9s} {'again':>9s} {'repeat':>7s} {'shape 16':>9s} {'change':>7s}  (ms; shape 32 = the faster of the two)")
+        su = sp = rep = 0.0
+        for k, (cnt, ms) in s16.items():
+            if k[1] not in ("cluster", "local") or (" 3x3/" in k[0]) != spatial:
+                continue
+            a, b = a1[k][1], a2[k][1]
+            base = min(a, b)
+            su += base
+            sp += ms
+            rep += abs(a - b)
+            print(f"{(str(cnt) + ' x ' + k[0]):34s} {a:9.2f} {b:9.2f} {abs(a - b) / base * 100:6.1f}% {ms:9.2f} {(ms - base) / base * 100:+6.1f}%")
+        if su:
+            print(f"{'sum':34s} {su:9.2f} {'':9s} {rep / su * 100:6.1f}% {sp:9.2f} {(sp - su) / su * 100:+6.1f}%")
+        print()
+elif args.pack != "ab":
+    if args.mfma:
+        os.environ["AVS_LOCAL224_MFMA"] = args.mfma
     runner.pack_groups = args.pack == "on"
     measure("")
 else:
