@@ -374,6 +374,10 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, 
   }
   cnt[threadIdx.x] = k;
   __syncthreads();
+  if (rt == 0 && ch < c && nrows <= 0) {  // a group with no rows: zeros (avs_segment_mean_f32's convention)
+#pragma unroll
+    for (int j = 0; j < V; ++j) scale[(long long)g * c + ch + j] = shift[(long long)g * c + ch + j] = 0.f;
+  }
   if (rt == 0 && active) {
 #pragma unroll
     for (int j = 0; j < V; ++j) {
@@ -435,6 +439,13 @@ __device__ __forceinline__ void storev(T* p, const float (&v)[V]) {
       w[j] = (unsigned)avs_f32_to_bf16(v[2 * j]) | ((unsigned)avs_f32_to_bf16(v[2 * j + 1]) << 16);
     *reinterpret_cast<uint4*>(p) = u;
   }
+}
+
+// The alignment an activation pointer needs for the vector accesses of the apply / pooling kernels: 16 bytes in fp32
+// (float4) and 8 bytes in bf16 (the narrow instance's uint2; the 8-wide instance is picked only where every pointer is
+// 16-byte aligned).  AVS_F16X2's 32 bytes are checked together with its strides.
+static inline bool avs_act_aligned(int dtype, const void* p) {
+  return (((uintptr_t)p) & (dtype == AVS_BF16 ? 7u : 15u)) == 0;
 }
 
 extern "C" int avs_bn_batch_stats(int dtype, const void* d_x, int64_t rows, int c, int64_t ldx,
@@ -529,6 +540,10 @@ extern "C" int avs_bn_apply(int dtype, const void* d_x, int64_t rows, int c, int
   AVS_REQUIRE((groups > 0) == (d_group_rows != nullptr), AVS_E_ARG, "avs_bn_apply: groups and d_group_rows disagree");
   if (rows == 0) return AVS_OK;
   AVS_REQUIRE(d_x && d_scale && d_shift && d_y, AVS_E_ARG, "avs_bn_apply: null pointer");
+  AVS_REQUIRE(avs_act_aligned(dtype, d_x) && avs_act_aligned(dtype, d_y) && avs_act_aligned(dtype, d_residual), AVS_E_ALIGN,
+              "avs_bn_apply: x, y and the residual must be 16-byte aligned (8-byte in bf16)");
+  AVS_REQUIRE(avs_aligned16(d_scale) && avs_aligned16(d_shift), AVS_E_ALIGN,
+              "avs_bn_apply: scale / shift must be 16-byte aligned");
   const bool wide = dtype == AVS_BF16 && c % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && (!d_residual || ldr % 8 == 0) &&
                     avs_aligned16(d_x) && avs_aligned16(d_y) && avs_aligned16(d_residual);
   const long long span = (groups > 0 ? max_group_rows : rows) * (c / ((wide || h2) ? 8 : 4));
@@ -644,6 +659,9 @@ extern "C" int avs_pool2d_nhwc(int dtype, int mode, const void* d_x, int n, int 
   AVS_REQUIRE((ho - 1) * s - p < h && (wo - 1) * s - p < w, AVS_E_SHAPE, "avs_pool2d_nhwc: output extent too large");
   if (n == 0) return AVS_OK;
   AVS_REQUIRE(d_x && d_y, AVS_E_ARG, "avs_pool2d_nhwc: null pointer");
+  AVS_REQUIRE(avs_act_aligned(dtype, d_x) && avs_act_aligned(dtype, d_y), AVS_E_ALIGN,
+              "avs_pool2d_nhwc: x and y must be 16-byte aligned (8-byte in bf16)");
+  AVS_REQUIRE((((uintptr_t)d_bias) & 3u) == 0, AVS_E_ALIGN, "avs_pool2d_nhwc: bias must be 4-byte aligned");
   const bool wide = dtype == AVS_BF16 && c % 8 == 0 && x_px_stride % 8 == 0 && y_px_stride % 8 == 0 &&
                     avs_aligned16(d_x) && avs_aligned16(d_y);
   const long long total = (long long)n * ho * wo * (c / ((wide || h2) ? 8 : 4));
@@ -760,6 +778,8 @@ extern "C" int avs_bn_maxpool_nhwc(int dtype, const void* d_x, int n, int h, int
               "avs_bn_maxpool_nhwc: groups and d_group_rows disagree");
   if (n == 0) return AVS_OK;
   AVS_REQUIRE(d_x && d_y && d_scale && d_shift, AVS_E_ARG, "avs_bn_maxpool_nhwc: null pointer");
+  AVS_REQUIRE(avs_act_aligned(dtype, d_x) && avs_act_aligned(dtype, d_y), AVS_E_ALIGN,
+              "avs_bn_maxpool_nhwc: x and y must be 16-byte aligned (8-byte in bf16)");
   AVS_REQUIRE(avs_aligned16(d_scale) && avs_aligned16(d_shift), AVS_E_ALIGN,
               "avs_bn_maxpool_nhwc: scale / shift must be 16-byte aligned");
   const bool wide = dtype == AVS_BF16 && c % 8 == 0 && x_px_stride % 8 == 0 && y_px_stride % 8 == 0 &&
@@ -825,6 +845,8 @@ extern "C" int avs_global_avgpool_nhwc(int dtype, const void* d_x, int n, int hw
   if (n == 0) return AVS_OK;
   AVS_REQUIRE(d_x && d_y, AVS_E_ARG, "avs_global_avgpool_nhwc: null pointer");
   AVS_REQUIRE(avs_aligned16(d_y), AVS_E_ALIGN, "avs_global_avgpool_nhwc: y not 16-byte aligned");
+  AVS_REQUIRE(avs_act_aligned(dtype, d_x), AVS_E_ALIGN,
+              "avs_global_avgpool_nhwc: x must be 16-byte aligned (8-byte in bf16)");
   const long long total = (long long)n * (c / (h2 ? 8 : 4));
   long long gx = avs_cdiv(total, 256);
   if (gx > 16384) gx = 16384;

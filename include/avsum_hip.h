@@ -402,7 +402,9 @@ int avs_resize_bilinear_u8(const uint8_t* d_src, int n, int sh, int sw,
  * statistics per (group, channel) over the rows of the group's frames, biased
  * variance, eps.  d_group_rows[g]..d_group_rows[g+1] are the row ranges of the
  * groups (a group = one micro-batch of <=4 frames, extractors.py:48-56).
- * Writes the folded affine  scale[g,c] = gamma*rstd,  shift[g,c] = beta - mean*scale. */
+ * Writes the folded affine  scale[g,c] = gamma*rstd,  shift[g,c] = beta - mean*scale.
+ * A group with no rows gets scale[g,:] = shift[g,:] = 0 (avs_segment_mean_f32's convention: empty -> zeros).
+ * Alignment: d_x 16 bytes (32 for AVS_F16X2); c and ldx multiples of 4 (8 for AVS_F16X2); else AVS_E_ALIGN / _SHAPE. */
 int avs_bn_batch_stats(int dtype, const void* d_x, int64_t rows, int c, int64_t ldx,
                        const int64_t* d_group_rows, int groups,
                        const float* d_gamma, const float* d_beta, float eps,
@@ -410,7 +412,11 @@ int avs_bn_batch_stats(int dtype, const void* d_x, int64_t rows, int c, int64_t 
 
 /* y = act( x*scale[g] + shift[g] (+ residual) ), rows of group g as above;
  * max_group_rows = the largest group's row count (sizes the launch).
- * groups==0 with d_group_rows NULL: one affine for all rows (folded eval BN). */
+ * groups==0 with d_group_rows NULL: one affine for all rows (folded eval BN).
+ * y may be x (in place), with or without a residual.
+ * Alignment (AVS_E_ALIGN otherwise): d_x, d_y and d_residual 16 bytes in fp32, 8 bytes in bf16 (16 bytes, with c and
+ * every stride a multiple of 8, selects the 8-wide bf16 kernel), 32 bytes in AVS_F16X2; d_scale / d_shift 16 bytes.
+ * c and the strides are multiples of 4 (8 for AVS_F16X2).                      */
 int avs_bn_apply(int dtype, const void* d_x, int64_t rows, int c, int64_t ldx,
                  const int64_t* d_group_rows, int groups, int64_t max_group_rows,
                  const float* d_scale, const float* d_shift,
@@ -424,7 +430,10 @@ int avs_bn_apply(int dtype, const void* d_x, int64_t rows, int c, int64_t ldx,
  * y = act(pool(x) + bias).  Inception's branch_pool (avg_pool2d 3x3/1 -> 1x1 conv -> folded BN -> ReLU,
  * torchvision inception.py as loaded at features/extractors.py:26) runs as 1x1 conv WITHOUT bias -> this call:
  * averaging and a 1x1 convolution commute (both linear; the zero padding of count_include_pad commutes too), and the
- * pooling then moves cout instead of cin channels (4-10x fewer).                                                   */
+ * pooling then moves cout instead of cin channels (4-10x fewer).
+ * Alignment (AVS_E_ALIGN otherwise): d_x and d_y 16 bytes in fp32, 8 bytes in bf16 (16 bytes, with c and both pixel
+ * strides a multiple of 8, selects the 8-wide bf16 kernel), 32 bytes in AVS_F16X2; d_bias 4 bytes.  c and the pixel
+ * strides are multiples of 4 (8 for AVS_F16X2).                                                                      */
 int avs_pool2d_nhwc(int dtype, int mode, const void* d_x, int n, int h, int w, int c,
                     int64_t x_px_stride, int k, int s, int p, const float* d_bias, int act, void* d_y,
                     int ho, int wo, int64_t y_px_stride, avs_stream_t stream);
@@ -432,13 +441,18 @@ int avs_pool2d_nhwc(int dtype, int mode, const void* d_x, int n, int h, int w, i
 /* BatchNorm apply + ReLU + max pooling in one pass: y = maxpool_{k,s,p}( act( x*scale[g] + shift[g] ) ), g = the
  * group (d_group_rows ranges over INPUT rows, as in avs_bn_apply; groups == 0 / NULL: one affine) of the image.
  * The ResNet stem's bn1 -> relu -> maxpool (features/extractors.py:29) without writing the normalised
- * full-resolution map; bit-identical to avs_bn_apply followed by avs_pool2d_nhwc(max).                      */
+ * full-resolution map; bit-identical to avs_bn_apply followed by avs_pool2d_nhwc(max) (AVS_F16X2: the same stored
+ * values - a value has more than one hi | lo image, and the two-kernel sequence splits twice).
+ * An image belongs to the last group whose range starts at or before the image's first row: an empty group owns none.
+ * Alignment (AVS_E_ALIGN otherwise): d_x and d_y as for avs_pool2d_nhwc; d_scale / d_shift 16 bytes.               */
 int avs_bn_maxpool_nhwc(int dtype, const void* d_x, int n, int h, int w, int c, int64_t x_px_stride,
                         const int64_t* d_group_rows, int groups, const float* d_scale, const float* d_shift,
                         int relu, int k, int s, int p, void* d_y, int ho, int wo, int64_t y_px_stride,
                         avs_stream_t stream);
 
-/* Global average pool: y[n,c] = mean over h*w (fp32 out).  (adaptive avgpool) */
+/* Global average pool: y[n,c] = mean over h*w (fp32 out).  (adaptive avgpool)
+ * Alignment (AVS_E_ALIGN otherwise): d_x 16 bytes in fp32, 8 bytes in bf16, 32 bytes in AVS_F16X2; d_y 16 bytes;
+ * c and ldy multiples of 4 (c of 8 for AVS_F16X2).                           */
 int avs_global_avgpool_nhwc(int dtype, const void* d_x, int n, int hw, int c,
                             float* d_y, int64_t ldy, avs_stream_t stream);
 
