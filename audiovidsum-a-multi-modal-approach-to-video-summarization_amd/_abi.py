@@ -164,6 +164,11 @@ _SIGNATURES = {
     "avs_mask_overlap_counts": (c_int, [P, P, c_int64, c_int, c_int64, P, c_int, P, P]),
     "avs_resize_bilinear_gather2_u8": (c_int, [P, c_int64, c_int, c_int, P, c_int64, P, c_int, c_int, P, c_int, c_int, P]),
     "avs_segment_mean_perm_f32": (c_int, [P, c_int64, c_int64, c_int, P, c_int64, P, c_int, P, c_int64, P]),
+    "avs_kts_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "avs_kts_gram_f64": (c_int, [P, c_int64, c_int, c_int64, c_int64, P, c_int, P, c_int64, P, c_int64, P]),
+    "avs_kts_scatters_f64": (c_int, [P, P, c_int, c_int, P, c_size_t, c_int64, c_int64, c_int64, c_int64, P, P]),
+    "avs_kts_dp_f64": (c_int, [P, c_int, c_int, c_int, c_int64, c_int, P, P, c_size_t, c_int64, c_int64, c_int64, c_int64,
+                               c_int64, P, P, P, P, P, P, P, P]),
 }
 
 _lib = None

@@ -156,17 +156,19 @@ def _upload_shot_lists(shot_lists, lengths, device):
 def keyshot_summaries_device(scores, video_offsets, shots, ratio=0.15):
     """The keyshot summary of every (score row, video) of a ragged batch in two launches, nothing read back.
     ``scores``: fp32 device [N] (one row) or [K, N]; ``video_offsets``: the host frame offsets [V + 1].  ``shots``: a
-    features.shots.ShotBatchResult - its device tables are used as they are, nothing is downloaded, shot_cap is its
-    plan's - or a list with one host list [(start, end)] per video (video-relative, inside the video, ascending, not
+    features.shots.ShotBatchResult or a features.kts.KtsResult (the segments of kernel temporal segmentation) - its
+    device tables are used as they are, nothing is downloaded, shot_cap is its plan's - or a list with one host list [(start, end)] per video (video-relative, inside the video, ascending, not
     overlapping), uploaded once.  Returns a KeyshotResult (its tensors keep the row dimension, K = 1 for a vector)."""
     import torch
     from .. import ops
+    from ..features.kts import KtsResult
     from ..features.shots import ShotBatchResult
     from ..ragged import RaggedOffsets
     if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
         raise ValueError("keyshot_summaries_device: scores must be a device tensor (there is no CPU fallback)")
-    if isinstance(shots, ShotBatchResult):
-        plan = ops.SummaryTables(video_offsets, ratio, shots.plan, scores.device)
+    if isinstance(shots, (ShotBatchResult, KtsResult)):
+        cap = shots.shot_cap if isinstance(shots, KtsResult) else shots.plan
+        plan = ops.SummaryTables(video_offsets, ratio, cap, scores.device)
         if not np.array_equal(plan.offsets, shots.plan.offsets):
             raise ValueError("keyshot_summaries_device: the shots were detected for other video offsets")
         shot_offsets, shot_table = shots.shot_offsets, shots.shots

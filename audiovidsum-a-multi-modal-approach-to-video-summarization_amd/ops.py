@@ -12,8 +12,9 @@ from . import _abi
 from ._abi import (ACT_NONE, ACT_RELU, AVS_BF16, AVS_F16X2, AVS_F32, AVS_F32_SPLIT, BIAS_COL, BIAS_NONE, BIAS_ROW, check,
                    lib)
 from .ragged import (EVAL_CHUNK, EVAL_MAX_T, EVAL_TILE, FUSION_MAX_N, FUSION_MID_L, FUSION_SMALL_L,  # noqa: F401
-                     SHOT_INTERVAL, SHOT_MAX_FRAMES, SHOT_MICRO_BATCH, SUMMARY_MAX_CAPACITY, SUMMARY_MAX_ROWS, EvalTables,
-                     FusionTables, RaggedOffsets, SeqTable, ShotTables, StageOneTables, SummaryTables)
+                     KTS_MAX_SAMPLES, SHOT_INTERVAL, SHOT_MAX_FRAMES, SHOT_MICRO_BATCH, SUMMARY_MAX_CAPACITY, SUMMARY_MAX_ROWS,
+                     EvalTables, FusionTables, KtsTables, RaggedOffsets, SeqTable, ShotTables, StageOneTables,
+                     SummaryTables)
 
 __all__ = [
     "ACT_NONE", "ACT_RELU", "linear", "gemm_nt_batched", "conv2d", "conv2d_raw", "conv2d_split", "conv_bnlocal_tile_rows", "conv_bncluster_ok", "conv_bnstats_ok", "cluster_exchange_errors", "lstm_split_errors", "conv1x1_bn", "conv1x1_gram_bn", "bn_gram_affine", "gram_supported", "frames_normalize", "pull_copy", "stem_conv_bn_pool", "stem_h2_operands", "stem_conv_pool_h2", "resize_bilinear",
@@ -24,6 +25,7 @@ __all__ = [
     "ShotTables", "hsv_frame_diff_batch", "shot_cuts_batch", "shot_tables", "gather_rows",
     "SummaryTables", "shot_value_sums", "knapsack_batch", "mask_overlap_counts",
     "StageOneTables", "resize_gather", "segment_mean_perm",
+    "KtsTables", "kts_workspace", "kts_gram", "kts_segment",
 ]
 
 
@@ -1928,3 +1930,66 @@ def mask_overlap_counts(tables_or_offsets, pred_mask, user_masks):
     check(lib().avs_mask_overlap_counts(_p(pred_mask), _p(user_masks), ld, u, n, _p(offsets_t), nv, _p(counts),
                                         _stream()), "avs_mask_overlap_counts")
     return counts
+
+
+# --------------------------------------------------------------------------- kernel temporal segmentation
+def kts_workspace(plan):
+    """Bytes of the workspace kts_segment takes for ``plan`` (an ops.KtsTables), asked of the library; the plan's own
+    ``workspace_bytes`` mirrors it."""
+    if not isinstance(plan, KtsTables):
+        raise ValueError("kts_workspace: plan must be an ops.KtsTables")
+    return int(lib().avs_kts_workspace_bytes(plan.k1_entries, plan.k_entries, plan.jt_entries, plan.p_entries))
+
+
+def kts_gram(plan, features):
+    """The packed fp64 Gram matrices of every video of the batch in ONE launch on the fp64 matrix cores: a device
+    tensor [plan.k_entries], video v's [n_v, n_v] row-major block at plan.k_offsets[v], K[i, j] = the fp64 sum of the
+    exact products of its samples i and j (rows offsets[v] + i * stride of ``features``).  ``features``: fp32 device
+    [N, D] with N = plan.frames, unit column stride and any row pitch >= D; it is read where it lies.  K is symmetric
+    to the bit and a video's block does not depend on the batch around it.  Nothing synchronises."""
+    what = "kts_gram"
+    _tables_arg(plan, KtsTables, what)
+    _device_arg(features, "features", what, (torch.float32,), ndim=2, device=plan.device, contiguous=False)
+    n, d = features.shape
+    if n != plan.frames or d < 1 or (d > 1 and features.stride(1) != 1) or (n > 1 and features.stride(0) < d):
+        raise ValueError(f"{what}: features must be [{plan.frames}, D >= 1] with unit column stride and a row pitch "
+                         f">= D, got shape {list(features.shape)} with strides {list(features.stride())}")
+    gram = torch.empty(plan.k_entries, dtype=torch.float64, device=plan.device)
+    check(lib().avs_kts_gram_f64(_p(features), n, d, max(features.stride(0), d) if n > 1 else d, plan.stride,
+                                 _p(plan.videos_t), plan.nvideos, _p(plan.tiles_t), plan.ntiles, _p(gram),
+                                 plan.k_entries, _stream()), "avs_kts_gram_f64")
+    return gram
+
+
+def kts_segment(plan, gram, select="auto"):
+    """Everything after the Gram matrix: the scatter tables, the dynamic programme, the model selection, the backtrack
+    and the shot table, five launches, nothing read back.  ``gram``: fp64 device [plan.k_entries], the packed K of
+    kts_gram or a caller's own kernel matrices in that layout (symmetric).  ``select``: "auto" = the smallest number of
+    change points of least penalised cost (cpd_auto), "fixed" = m_max of the plan.  Returns a dict of device tensors:
+    ``change_points`` int64 [shot_cap] (video v's ascending sample indices from plan.cost_offsets[v], -1 after them),
+    ``shot_offsets`` int64 [V + 1] and ``shots`` int64 [shot_cap, 2] (video-relative frame rows, the layout of
+    ops.shot_tables), ``scores`` and ``costs`` float64 [shot_cap] (I_k[n] and the penalised cost of k change points at
+    plan.cost_offsets[v] + k), ``totals`` int64 [V, 4] = (m_best, n, m_max, flag) and ``flags`` int64 [V]; a video
+    whose K holds a NaN or an Inf is flagged: one shot, NaN costs."""
+    what = "kts_segment"
+    _tables_arg(plan, KtsTables, what)
+    if select not in ("auto", "fixed"):
+        raise ValueError(f"{what}: select must be 'auto' or 'fixed', got {select!r}")
+    _device_arg(gram, "gram", what, (torch.float64,), shape=(plan.k_entries,), device=plan.device)
+    dev, v, cap = plan.device, plan.nvideos, plan.shot_cap
+    ws = torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=dev)
+    flags = torch.empty(v, dtype=torch.int64, device=dev)
+    entries = (plan.k1_entries, plan.k_entries, plan.jt_entries, plan.p_entries)
+    check(lib().avs_kts_scatters_f64(_p(gram), _p(plan.videos_t), v, plan.max_n, _p(ws), plan.workspace_bytes, *entries,
+                                     _p(flags), _stream()), "avs_kts_scatters_f64")
+    out = {"change_points": torch.empty(cap, dtype=torch.int64, device=dev),
+           "shot_offsets": torch.empty(v + 1, dtype=torch.int64, device=dev),
+           "shots": torch.empty((cap, 2), dtype=torch.int64, device=dev),
+           "scores": torch.empty(cap, dtype=torch.float64, device=dev),
+           "costs": torch.empty(cap, dtype=torch.float64, device=dev),
+           "totals": torch.empty((v, 4), dtype=torch.int64, device=dev), "flags": flags}
+    check(lib().avs_kts_dp_f64(_p(plan.videos_t), v, plan.max_n, plan.lmin, plan.stride, int(select == "fixed"),
+                               _p(plan.penalties_t), _p(ws), plan.workspace_bytes, *entries, cap, _p(flags),
+                               _p(out["scores"]), _p(out["costs"]), _p(out["change_points"]), _p(out["shot_offsets"]),
+                               _p(out["shots"]), _p(out["totals"]), _stream()), "avs_kts_dp_f64")
+    return out

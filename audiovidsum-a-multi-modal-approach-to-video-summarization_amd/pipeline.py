@@ -11,6 +11,7 @@ import torch
 from . import ops
 from .evaluation.keyshots import keyshot_summaries_device
 from .evaluation.metrics import select_frames, select_mask_device
+from .features.kts import kts_batch_device
 
 
 class _HostStager:
@@ -323,6 +324,14 @@ class FrameScoringPipeline:
     def summarize_device(scores, video_offsets, shots, ratio=0.15):
         """The keyshot summary of every video: whole shots chosen by a 0/1 knapsack (value = the shot's mean score,
         weight = its length, capacity = ``ratio`` of the video), on the device.  ``shots``: the ShotBatchResult of
-        features.shots.detect_shots_batch, used where it lies, or one host [(start, end)] list per video.  Returns the
-        evaluation.keyshots.KeyshotResult: mask, picked, optimum and totals stay on the device until its host()."""
+        features.shots.detect_shots_batch or the KtsResult of segment_device, used where it lies, or one host
+        [(start, end)] list per video.  Returns the evaluation.keyshots.KeyshotResult: mask, picked, optimum and totals
+        stay on the device until its host()."""
         return keyshot_summaries_device(scores, video_offsets, shots, ratio)
+
+    @staticmethod
+    def segment_device(features, video_offsets, **kw):
+        """Kernel temporal segmentation of every video on its per-frame embeddings (embed()'s [N, 4096], where they
+        lie): features.kts.kts_batch_device with its keywords (stride, ncp, vmax, lmin, select).  Returns the
+        features.kts.KtsResult, which summarize_device takes as ``shots``."""
+        return kts_batch_device(features, video_offsets, **kw)

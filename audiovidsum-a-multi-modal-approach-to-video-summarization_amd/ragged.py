@@ -1,10 +1,12 @@
 """Host plans of the ragged-batch layers: row offsets validated on the host and uploaded once (RaggedOffsets and the
-five tables built on it - EvalTables, SeqTable, ShotTables, StageOneTables, SummaryTables) and the pair tables of the
+six tables built on it - EvalTables, SeqTable, ShotTables, StageOneTables, SummaryTables, KtsTables) and the pair tables of the
 batched fusion (FusionTables).
 Pure host code on numpy and torch: nothing here touches the kernel library, so the plans can be built and checked with
 ``device="cpu"`` where there is no GPU.  ops.py re-exports every name and holds the launch wrappers that take them."""
 import numpy as np
 import torch
+
+from .features.kts import KTS_MAX_SAMPLES, kts_penalties   # (pure numpy: the limit and the penalty of the definitions)
 
 FUSION_MAX_N = 6400      # rows of the visual side of one pair (the per-pair limit of dtw_path)
 FUSION_SMALL_L = 64      # size classes by l = min(n, m): l <= 64 one wave per pair (four pairs per workgroup),
@@ -23,6 +25,10 @@ SUMMARY_MAX_CAPACITY = 8191   # knapsack cells 0 .. capacity: two fp64 rows of 8
 SUMMARY_MAX_ROWS = 1024       # score rows of one knapsack batch (grid y).  The take-bit workspace holds rows * shot_cap *
                               # words uint64 entries with words <= 128: below 2^31 for every shot_cap below 2^14 = 16 384
                               # at the full 1024 rows and 8191 cells; past that the wrapper refuses by take_words itself
+
+# KTS_MAX_SAMPLES (2048, from features/kts.py): samples of one video - the two fp64 rows of the dynamic programme live in LDS
+KTS_TILE = 64           # rows and columns of a Gram tile
+KTS_MAX_VIDEOS = 65535   # videos of one batch (a grid dimension)
 
 
 def exclusive_offsets(lengths):
@@ -277,6 +283,86 @@ class SummaryTables(RaggedOffsets):
     def take_words(self, k):
         """uint64 entries of the take-bit workspace [k][shot_cap][words] of a knapsack batch of ``k`` score rows."""
         return int(k) * self.shot_cap * self.words
+
+
+class KtsTables(RaggedOffsets):
+    """The host plan of one batch layout for kernel temporal segmentation (kts_gram, kts_segment), built once from the
+    host frame offsets [V + 1] of the videos in the concatenated feature rows, the subsampling ``stride``, ``ncp`` (the
+    most change points tried: None = n - 1, an int, or one entry per video, None among them), ``vmax`` (the weight of
+    cpd_auto's penalty) and ``lmin`` (the shortest segment, in samples).
+
+    Host side (numpy): ``offsets``, ``lengths``, ``nvideos``, ``frames``; ``n`` int64 [V] = ceil(N_v / stride), the
+    samples of a video (sample i is its row i * stride), ``max_n``; ``m_max`` int64 [V] = max(0, min(ncp, n // lmin -
+    1)); ``k_offsets`` [V + 1], the exclusive sums of n^2: video v's [n, n] row-major block of the packed fp64 Gram
+    buffer (``k_entries`` in all); ``k1_offsets`` over n + 1, ``jt_offsets`` over (n + 1)^2 and ``p_offsets`` over
+    (m_max + 1)(n + 1): the blocks of K1, Jt[l][t] and p_k[l] in the workspace; ``cost_offsets`` over m_max + 1 and
+    ``cost_cap`` = ``shot_cap`` = their total: the slots of the costs, the change points and the shots;
+    ``penalties`` float64 [cost_cap] (kts_penalties per video); ``tiles`` int32 [ntiles, 3] = (video, ti, tj) with
+    ti <= tj, the 64 x 64 tiles of the upper triangles; ``workspace_bytes`` (= avs_kts_workspace_bytes of the entries).
+    Device side: ``offsets_t``, ``videos_t`` int64 [V, 10] (the per-video row of all of the above, the layout
+    include/avsum_hip.h gives), ``tiles_t``, ``penalties_t``.  ``device="cpu"`` keeps everything on the host (the builder
+    can be checked without a GPU).  Refused, each with a ValueError: what SeqTable refuses about the offsets, more than
+    65535 videos, stride < 1, lmin < 1, a video of more than 2048 samples, ncp < 0 (or a list of another length than
+    V), a vmax that is not finite or is <= 0, a packed size of 2^31 entries or more."""
+
+    def __init__(self, video_offsets, stride=15, ncp=None, vmax=1.0, lmin=1, device=None):
+        super().__init__(video_offsets, "KtsTables", device=device)
+        if int(stride) < 1 or int(lmin) < 1:
+            raise ValueError(f"KtsTables: stride and lmin must be >= 1, got stride = {stride}, lmin = {lmin}")
+        vmax = float(vmax)
+        if not (np.isfinite(vmax) and vmax > 0.0):
+            raise ValueError(f"KtsTables: vmax must be finite and > 0, got {vmax}")
+        if self.count > KTS_MAX_VIDEOS:
+            raise ValueError(f"KtsTables: {self.count} videos, a batch takes at most {KTS_MAX_VIDEOS}")
+        self.nvideos, self.frames = self.count, self.total
+        self.stride, self.lmin, self.vmax = int(stride), int(lmin), vmax
+        self.n = -(-self.lengths // self.stride)
+        self.max_n = int(self.n.max())
+        if self.max_n > KTS_MAX_SAMPLES:
+            v = int(np.argmax(self.n))
+            raise ValueError(f"KtsTables: video {v} has {int(self.n[v])} samples at stride {self.stride}, above the "
+                             f"LDS-resident limit {KTS_MAX_SAMPLES}")
+        if ncp is None or np.isscalar(ncp):
+            ncp = [ncp] * self.nvideos
+        ncp = list(ncp)
+        if len(ncp) != self.nvideos:
+            raise ValueError(f"KtsTables: {len(ncp)} ncp entries for {self.nvideos} videos")
+        self.ncp = np.array([int(nv) - 1 if c is None else int(c) for c, nv in zip(ncp, self.n)], dtype=np.int64)
+        if (self.ncp < 0).any():
+            raise ValueError(f"KtsTables: ncp must be >= 0, got {int(self.ncp.min())}")
+        self.m_max = np.maximum(0, np.minimum(self.ncp, self.n // self.lmin - 1))
+        self.k_offsets = exclusive_offsets(self.n * self.n)
+        self.k1_offsets = exclusive_offsets(self.n + 1)
+        self.jt_offsets = exclusive_offsets((self.n + 1) * (self.n + 1))
+        self.p_offsets = exclusive_offsets((self.m_max + 1) * (self.n + 1))
+        self.cost_offsets = exclusive_offsets(self.m_max + 1)
+        self.k_entries, self.k1_entries = int(self.k_offsets[-1]), int(self.k1_offsets[-1])
+        self.jt_entries, self.p_entries = int(self.jt_offsets[-1]), int(self.p_offsets[-1])
+        self.cost_cap = self.shot_cap = int(self.cost_offsets[-1])
+        nt = -(-self.n // KTS_TILE)
+        upper = [np.triu_indices(int(t)) for t in nt]                  # (ti, tj), ti <= tj, row by row
+        self.tiles = np.concatenate([np.stack([np.full(ti.size, v), ti, tj], 1) for v, (ti, tj) in enumerate(upper)])
+        self.tiles = self.tiles.astype(np.int32).reshape(-1, 3)
+        self.ntiles = self.tiles.shape[0]
+        for name, entries in (("Gram", self.k_entries), ("Jt", self.jt_entries), ("p", self.p_entries),
+                              ("tile", self.ntiles)):
+            if entries >= 1 << 31:
+                raise ValueError(f"KtsTables: the packed {name} buffer needs {entries} entries, the kernels take fewer "
+                                 "than 2^31")
+        self.penalties = np.concatenate([kts_penalties(nv, mm, vmax) for nv, mm in zip(self.n, self.m_max)])
+        self.workspace_bytes = sum((int(b) + 255) & ~255 for b in (8 * self.k1_entries, 8 * self.k_entries,
+                                                                   8 * self.jt_entries, 2 * self.p_entries))
+        self.videos = np.zeros((self.nvideos, 10), dtype=np.int64)
+        for col, x in enumerate((self.offsets[:-1], self.lengths, self.n, self.m_max, self.k_offsets[:-1],
+                                 self.k1_offsets[:-1], self.jt_offsets[:-1], self.p_offsets[:-1], self.cost_offsets[:-1])):
+            self.videos[:, col] = x
+        self.videos_t, self.tiles_t, self.penalties_t = _upload(self.device, self.videos, self.tiles, self.penalties)
+
+    def shots_of(self, v, change_points):
+        """The [(start, end)] list, in video-relative FRAME rows, that ``change_points`` (ascending sample indices)
+        cut video ``v`` into: b_0 = 0, b_j = cp[j - 1] * stride, the last end N_v."""
+        b = [0] + [int(c) * self.stride for c in change_points] + [int(self.lengths[v])]
+        return list(zip(b[:-1], b[1:]))
 
 
 class FusionTables:

@@ -929,6 +929,46 @@ int avs_segment_mean_perm_f32(const float* d_x, int64_t ldx, int64_t x_rows, int
                               int64_t perm_len, const int64_t* d_seg, int nseg, float* d_out, int64_t ldo,
                               avs_stream_t stream);
 
+/* ---- kernel temporal segmentation of a ragged batch (csrc/kts.hip; the definitions: features/kts.py) ----------------
+ * The host plan (ops.KtsTables) gives d_videos int64 [nvideos][10] = per video (first feature row, frames N, samples
+ * n = ceil(N / stride) <= 2048, m_max, first entry of its block in the packed K / R buffers [n][n], in K1 [n + 1], in
+ * Jt [n + 1][n + 1], in p [m_max + 1][n + 1], in the cost / change-point / shot slots [m_max + 1], 0) and the packed
+ * sizes: k1_entries, k_entries, jt_entries, p_entries, cost_cap, each below 2^31.  The table is trusted.  The workspace
+ * holds K1 | R | Jt (fp64) | p (uint16), each part at a multiple of 256 bytes: avs_kts_workspace_bytes (0 for sizes out
+ * of range).  nvideos <= 65535.  No atomics; no kernel waits on another workgroup; nothing allocates or synchronises. */
+size_t avs_kts_workspace_bytes(int64_t k1_entries, int64_t k_entries, int64_t jt_entries, int64_t p_entries);
+
+/* d_gram[k_off_v + i * n + j] = sum over c < d of double(x_i[c]) * double(x_j[c]) on v_mfma_f64_16x16x4_f64, x_i = row
+ * first_row_v + i * stride of d_x fp32 [rows, d] with row pitch ld >= d (4-byte alignment suffices; read in place).
+ * d_tiles int32 [ntiles][3] = (video, ti, tj) with ti <= tj: the 64 x 64 tiles of the upper triangles.  The elements
+ * i <= j are stored to [i][j] and [j][i] from one register: K is symmetric to the bit, and a video's block does not
+ * depend on the batch around it.                                                                                      */
+int avs_kts_gram_f64(const float* d_x, int64_t rows, int d, int64_t ld, int64_t stride, const int64_t* d_videos,
+                     int nvideos, const int* d_tiles, int64_t ntiles, double* d_gram, int64_t k_entries,
+                     avs_stream_t stream);
+
+/* K1 (the sequential sums of the diagonal), R = cumsum(cumsum(K, 0), 1) (both strictly sequential; K2[a][b] =
+ * R[a - 1][b - 1], 0 on the first row and column) and Jt[l][t] = (K1[l] - K1[t]) - (((K2[l][l] + K2[t][t]) - K2[l][t])
+ * - K2[t][l]) / double(l - t) for 0 <= t < l <= n into the workspace; d_flags int64 [nvideos]: 1 where K2[n][n] is not
+ * finite.  Three launches; max_n: the largest n of the plan.                                                          */
+int avs_kts_scatters_f64(const double* d_gram, const int64_t* d_videos, int nvideos, int max_n, void* d_ws,
+                         size_t ws_bytes, int64_t k1_entries, int64_t k_entries, int64_t jt_entries, int64_t p_entries,
+                         int64_t* d_flags, avs_stream_t stream);
+
+/* The dynamic programme on the Jt of avs_kts_scatters_f64, one workgroup of 1024 threads per video (both live rows in
+ * LDS): I_0[l] = Jt[l][0]; I_k[l] = min over t = k lmin .. l - lmin of I_{k-1}[t] + Jt[l][t], p_k[l] the smallest t
+ * attaining it; d_scores[c_off_v + k] = I_k[n], d_costs[..] = score / double(n) + d_penalties[c_off_v + k] (fp64
+ * [cost_cap], from the host).  m_best = the smallest k of least cost (select_fixed = 0) or m_max; a flagged video gets
+ * m_best = 0 and NaN costs.  d_change_points int64 [cost_cap]: m_best ascending sample indices per video slot, -1
+ * after them.  d_totals int64 [nvideos][4] = (m_best, n, m_max, flag).  A second launch writes d_shot_offsets int64
+ * [nvideos + 1] (exclusive prefix of m_best + 1) and d_shots int64 [cost_cap][2], the layout of avs_shot_tables_fill:
+ * (b_j, b_{j+1}) with b_0 = 0, b_j = change point j - 1 times stride, the last end N; zeros past the last shot.       */
+int avs_kts_dp_f64(const int64_t* d_videos, int nvideos, int max_n, int lmin, int64_t stride, int select_fixed,
+                   const double* d_penalties, void* d_ws, size_t ws_bytes, int64_t k1_entries, int64_t k_entries,
+                   int64_t jt_entries, int64_t p_entries, int64_t cost_cap, const int64_t* d_flags, double* d_scores,
+                   double* d_costs, int64_t* d_change_points, int64_t* d_shot_offsets, int64_t* d_shots,
+                   int64_t* d_totals, avs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
