@@ -1,4 +1,5 @@
-"""ctypes binding of libavsum_hip.so (the C-ABI declared in include/avsum_hip.h).
+"""ctypes binding of libavsum_hip.so, DERIVED from include/avsum_hip.h: the argument types of every entry point, the
+fields of ConvDesc, the enum values and the ABI version are what _header.py reads there - none is typed here.
 
 The product path has no CPU fallback: if the library is missing, or a call
 returns a non-zero status, this module raises.  Build with
@@ -6,12 +7,14 @@ returns a non-zero status, this module raises.  Build with
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint, c_void_p
+from ctypes import c_int, c_int64
 
 # torch first: its HIP runtime (torch/lib/libamdhip64) must be the one this process initialises.  Loading
 # libavsum_hip.so before torch pulls in /opt/rocm's copy of the same SONAME instead, and the second runtime to come
 # up then reports "no ROCm-capable device".
 import torch  # noqa: F401  (memory, streams and the HIP runtime come from here)
+
+from ._header import HEADER_PATH, load as _load_header  # noqa: F401  (HEADER_PATH: where the contract lies)
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # AVS_STUDY_LIB=1 loads the kernel-study build (`make study`: the same library with the ablation switches of tools/
@@ -22,18 +25,28 @@ STUDY = os.environ.get("AVS_STUDY_LIB") == "1"
 _FLAVOUR = os.environ.get("AVS_STUDY_LIB")
 LIB_PATH = os.path.join(_PKG_DIR, "lib", "libavsum_hip_study.so" if STUDY else
                         "libavsum_hip_fp16emu.so" if _FLAVOUR == "fp16emu" else "libavsum_hip.so")
-HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "avsum_hip.h")
 
-AVS_F32, AVS_BF16, AVS_F32_ACC64, AVS_F32_SPLIT, AVS_F16X2 = 0, 1, 2, 3, 4
-AVS_W_ROWS, AVS_W_KSTEP32 = 0, 1
-TILE_AUTO, TILE_128, TILE_256, TILE_224, STAGING_GENERIC = 0, 1, 2, 3, 4      # avs_conv_desc.variant
-CLUSTER_PACKED = 8                                                            # ... the packed clustered BatchNorm (bit 3)
-X_F16P8, Y_F16P8, RES_F16P8 = 1, 2, 4                                         # avs_conv_desc.formats
-LSTM_AUTO, LSTM_STREAM, LSTM_RESIDENT_20_8, LSTM_RESIDENT_16_8 = 0, 1, 2, 3
+_HEADER = _load_header()
+SHARED = _HEADER.constants     # every enumerator and shared size of the header by its C name
+
+
+def _enum(names):
+    """The header's values of the enumerators AVS_<name>, in the order given."""
+    return tuple(_HEADER.constants["AVS_" + n] for n in names.split())
+
+
+AVS_F32, AVS_BF16, AVS_F32_ACC64, AVS_F32_SPLIT, AVS_F16X2 = _enum("F32 BF16 F32_ACC64 F32_SPLIT F16X2")
+AVS_W_ROWS, AVS_W_KSTEP32 = _enum("W_ROWS W_KSTEP32")
+TILE_AUTO, TILE_128, TILE_256, TILE_224 = _enum("TILE_AUTO TILE_128 TILE_256 TILE_224")    # avs_conv_desc.variant
+STAGING_GENERIC, CLUSTER_PACKED = _enum("STAGING_GENERIC CLUSTER_PACKED")                  # ... its bits 2 and 3
+X_F16P8, Y_F16P8, RES_F16P8 = _enum("X_F16P8 Y_F16P8 RES_F16P8")                           # avs_conv_desc.formats
+LSTM_AUTO, LSTM_STREAM, LSTM_RESIDENT_20_8, LSTM_RESIDENT_16_8 = _enum(
+    "LSTM_AUTO LSTM_STREAM LSTM_RESIDENT_20_8 LSTM_RESIDENT_16_8")
 LSTM_SPLIT4 = 4   # (host-side choice: the avs_lstm*_split_f32 entry points - one recurrence over four CUs)
-ACT_NONE, ACT_RELU = 0, 1
-BIAS_NONE, BIAS_COL, BIAS_ROW = 0, 1, 2
-E_UNSUPPORTED = -6
+ACT_NONE, ACT_RELU = _enum("ACT_NONE ACT_RELU")
+BIAS_NONE, BIAS_COL, BIAS_ROW = _enum("BIAS_NONE BIAS_COL BIAS_ROW")
+E_UNSUPPORTED, = _enum("E_UNSUPPORTED")
+ABI_VERSION, = _enum("ABI_VERSION")
 
 
 class AvsError(RuntimeError):
@@ -41,145 +54,19 @@ class AvsError(RuntimeError):
 
 
 class ConvDesc(ctypes.Structure):
-    _fields_ = [
-        ("dtype", c_int),
-        ("n", c_int), ("h", c_int), ("w", c_int),
-        ("cin", c_int), ("kh", c_int), ("kw", c_int),
-        ("sh", c_int), ("sw", c_int), ("ph", c_int), ("pw", c_int),
-        ("ho", c_int), ("wo", c_int), ("cout", c_int),
-        ("x_img_stride", c_int64), ("x_row_stride", c_int64), ("x_px_stride", c_int64),
-        ("w_row_stride", c_int64), ("y_px_stride", c_int64),
-        ("act", c_int), ("alpha", c_float), ("w_layout", c_int), ("variant", c_int), ("formats", c_int),
-    ]
+    _fields_ = _HEADER.fields("avs_conv_desc")
 
 
-P = c_void_p  # device pointer
-_SIGNATURES = {
-    "avs_abi_version": (c_int, []),
-    "avs_last_error": (c_char_p, []),
-    "avs_device_info": (c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int64), c_char_p, c_int]),
-    "avs_f16x2_pack_f32": (c_int, [P, P, c_int64, P]),
-    "avs_f16x2_unpack_f32": (c_int, [P, P, c_int64, P]),
-    "avs_f16p8_pack_f32": (c_int, [P, P, c_int64, P]),
-    "avs_f16p8_unpack_f32": (c_int, [P, P, c_int64, P]),
-    "avs_conv2d_nhwc": (c_int, [POINTER(ConvDesc), P, P, P, P, P]),
-    "avs_conv2d_bnstats_workspace_bytes": (c_int64, [POINTER(ConvDesc), c_int64]),
-    "avs_conv2d_nhwc_bnstats": (c_int, [POINTER(ConvDesc), P, P, P, c_int64, P, P, c_float, P, P, P, c_int64, P]),
-    "avs_conv2d_nhwc_bnstats_xin": (c_int, [POINTER(ConvDesc), P, P, P, c_int64, P, P, c_float, P, P, P, c_int64, P, P,
-                                            c_int, P]),
-    "avs_conv1x1_bn_bf16": (c_int, [P, c_int64, c_int, P, c_int64, c_int, c_int64, c_int, P, P, c_float, P, c_int64,
-                                    c_int, P, c_int64, P]),
-    "avs_conv1x1_bn_in_bf16": (c_int, [P, c_int64, c_int, P, P, P, c_int64, c_int, c_int64, c_int, P, P, c_float, P,
-                                       c_int64, c_int, P, c_int64, P]),
-    "avs_stem_workspace_bytes": (c_int64, [c_int]),
-    "avs_stem_conv_bn_pool_bf16": (c_int, [P, c_int, c_float, POINTER(c_float), POINTER(c_float), P, c_int64, c_int, P, P,
-                                           c_float, c_int, c_int, P, P, P, P, c_int64, P]),
-    "avs_stem_f16x2_workspace_bytes": (c_int64, [c_int]),
-    "avs_stem_conv_pool_f16x2": (c_int, [P, c_int, P, c_int64, c_int, P, P, c_float, P, P, P, P, c_int64, P]),
-    "avs_bn_gram_affine_bf16": (c_int, [P, c_int64, c_int, P, P, P, c_int64, c_int, c_int64, c_int, P, P, c_float, P, P,
-                                        P, c_int64, P]),
-    "avs_conv1x1_affine_bf16": (c_int, [P, c_int64, c_int, P, P, P, c_int64, c_int, c_int64, c_int, P, P, P, c_int64,
-                                        P, P, c_int, P, c_int64, P]),
-    "avs_bn_gram_affine_f16x2": (c_int, [P, c_int64, c_int, P, P, P, c_int64, c_int, c_int64, c_int, P, P, c_float, P, P,
-                                         P, c_int64, P]),
-    "avs_conv2d_nhwc_affine": (c_int, [POINTER(ConvDesc), P, P, P, c_int64, P, P, P, c_int64, P, P, P]),
-    "avs_conv2d_nhwc_split": (c_int, [POINTER(ConvDesc), P, P, P, P, c_int, P, c_int64, c_int, P]),
-    "avs_conv2d_bnlocal_tile_rows": (c_int, [POINTER(ConvDesc), c_int64]),
-    "avs_conv2d_nhwc_bnlocal": (c_int, [POINTER(ConvDesc), P, P, P, c_int64, P, P, c_float, P, c_int64, P]),
-    "avs_conv2d_bncluster_workspace_bytes": (c_int64, [POINTER(ConvDesc), c_int64, c_int]),
-    "avs_conv2d_nhwc_bncluster": (c_int, [POINTER(ConvDesc), P, P, P, c_int64, c_int, P, P, c_float, P, c_int64, P, c_int64,
-                                          c_uint, P]),
-    "avs_gemm_nt": (c_int, [c_int, c_int, c_int, c_int, P, c_int64, c_int64, P, c_int64, c_int64, P, c_int64,
-                            c_int64, P, c_int, c_int64, c_float, c_int, c_int, P]),
-    "avs_pull_copy_u8": (c_int, [P, P, c_int64, c_int, P]),
-    "avs_frames_normalize_u8": (c_int, [c_int, P, c_int, c_int, c_int, c_float, POINTER(c_float), POINTER(c_float),
-                                        POINTER(c_float), P, c_int, c_int, c_int, c_int, P]),
-    "avs_resize_bilinear_u8": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P]),
-    "avs_bn_batch_stats": (c_int, [c_int, P, c_int64, c_int, c_int64, P, c_int, P, P, c_float, P, P, P]),
-    "avs_bn_apply": (c_int, [c_int, P, c_int64, c_int, c_int64, P, c_int, c_int64, P, P, P, c_int64, c_int, P,
-                             c_int64, P]),
-    "avs_pool2d_nhwc": (c_int, [c_int, c_int, P, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, P, c_int, P,
-                                c_int, c_int, c_int64, P]),
-    "avs_bn_maxpool_nhwc": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_int64, P, c_int, P, P, c_int, c_int, c_int,
-                                    c_int, P, c_int, c_int, c_int64, P]),
-    "avs_global_avgpool_nhwc": (c_int, [c_int, P, c_int, c_int, c_int, P, c_int64, P]),
-    "avs_segment_mean_f32": (c_int, [P, c_int64, c_int, P, c_int, P, c_int64, P]),
-    "avs_hsv_frame_diff_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
-    "avs_reflect_pad_f32": (c_int, [P, c_int64, c_int, P, c_int64, P]),
-    "avs_stft_f64": (c_int, [P, c_int64, c_int64, c_int, c_int, P, c_int, c_int, P, P]),
-    "avs_stft_mel_fused_f32": (c_int, [P, c_int64, P, P, P, P, P, P, c_int, P, P, P, P, P]),
-    "avs_stft_mel_segmean_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "avs_stft_mel_segmean_f32": (c_int, [P, c_int64, P, P, P, P, P, P, c_int, P, c_int, P, P, c_int, P, c_int, c_float, P,
-                                         c_int64, P, c_int64, P, c_int64, P]),
-    "avs_stft_mel_segmean_batch_f32": (c_int, [P, P, P, c_int, P, P, P, P, P, P, c_int, P, c_int, P, P, c_int, P, c_float, P,
-                                               c_int64, P, c_int64, P, c_int64, P]),
-    "avs_stft_mel_shots_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
-    "avs_stft_mel_shots_f32": (c_int, [P, c_int64, P, P, c_int, P, c_int, P, P, P, P, P, P, c_int, P, c_int, P, P, P, c_float,
-                                       P, c_int64, P, c_int64, P, c_int64, P]),
-    "avs_vggish_examples_workspace_bytes": (c_int64, [c_int64]),
-    "avs_vggish_examples_f32": (c_int, [P, c_int64, P, c_int64, P, c_int, P, P, P, c_int, P, P, c_int64, P]),
-    "avs_power_mel_f32": (c_int, [P, c_int64, c_int, P, P, P, c_int, c_int, P, P, P]),
-    "avs_clamp_topdb_f32": (c_int, [P, c_int64, P, c_float, P]),
-    "avs_fill_f32": (c_int, [P, c_int64, c_float, P]),
-    "avs_quantize_f32": (c_int, [P, c_int64, c_float, c_float, c_float, P, P]),
-    "avs_resample_f32": (c_int, [P, c_int64, c_int, P, c_int, c_int, c_int, c_int, P, c_int64, P]),
-    "avs_lstm_f32": (c_int, [P, P, c_int, c_int, c_uint, P, c_int, P, c_int64, c_int, c_int, P]),
-    "avs_mha_batchaxis_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
-    "avs_score_head_f32": (c_int, [P, c_int64, c_int, c_int64, P, P, P, P]),
-    "avs_mhsa_flash_f32": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, c_int, P, c_int64, P]),
-    "avs_mhsa_flash_f16x2": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, c_int, P, c_int64, P]),
-    "avs_softmax_rows_f32": (c_int, [P, c_int64, c_int, c_int64, P]),
-    "avs_softmax_bwd_rows_f32": (c_int, [P, P, c_int64, c_int, c_int64, c_float, P]),
-    "avs_transpose_f32": (c_int, [P, c_int, c_int, c_int64, P, c_int64, P]),
-    "avs_colsum_f32": (c_int, [P, c_int64, c_int, c_int64, P, P, P]),
-    "avs_relu_dropout_bwd_f32": (c_int, [P, P, P, c_int64, P, P]),
-    "avs_mul_f32": (c_int, [P, P, c_int64, P, P]),
-    "avs_score_head_bwd_f32": (c_int, [P, P, P, c_int64, c_int, c_int64, P, P, P, P]),
-    "avs_lstm_train_fwd_f32": (c_int, [P, P, c_int, c_int, c_uint, P, c_int, P, c_int64, c_int, P, P, c_int, P]),
-    "avs_lstm_bwd_f32": (c_int, [P, c_int64, c_int, P, P, P, c_int, c_int, c_uint, P, c_int, P, c_int, P]),
-    "avs_lstm_split_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "avs_lstm_split_f32": (c_int, [P, P, c_int, c_int, c_uint, P, c_int, P, c_int64, c_int, P, P, P, c_size_t, c_uint, P]),
-    "avs_lstm_bwd_split_f32": (c_int, [P, c_int64, c_int, P, P, P, c_int, c_int, c_uint, P, c_int, P, P, c_size_t, c_uint, P]),
-    "avs_cdist_f64": (c_int, [P, c_int, P, c_int, c_int, P, P]),
-    "avs_dtw_workspace_bytes": (c_int64, [c_int, c_int]),
-    "avs_dtw_path_f64": (c_int, [P, c_int, c_int, P, c_int64, P, P, P, P]),
-    "avs_gather_scale_f32": (c_int, [P, c_int64, c_int, P, P, c_int, P, P]),
-    "avs_cdist_batch_f64": (c_int, [P, c_int64, P, c_int64, c_int, P, c_int, P, c_int64, P, c_int64, P]),
-    "avs_dtw_batch_workspace_bytes": (c_int64, [c_int64]),
-    "avs_dtw_batch_f64": (c_int, [P, c_int64, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int64,
-                                  P, P, P, P, P]),
-    "avs_fused_gather_batch_f32": (c_int, [P, c_int64, c_int, P, c_int, P, c_int64, P, P, P, c_int64, P, P]),
-    "avs_segment_mean_mask": (c_int, [P, c_int, c_int64, P, c_int, P, P, P]),
-    "avs_rank_pair_counts": (c_int, [P, P, c_int, c_int64, P, c_int, P, c_int64, c_int, P, P]),
-    "avs_eval_fold": (c_int, [P, P, P, c_int64, P, c_int, c_int, P, P]),
-    "avs_seq_shift_rows_f32": (c_int, [P, c_int64, c_int, c_int, c_int64, P, c_int, c_int, P, c_int64, P]),
-    "avs_seq_mse_f32": (c_int, [P, P, c_int, c_int64, P, c_int, P, P]),
-    "avs_seq_mse_bwd_f32": (c_int, [P, P, P, c_int, c_int64, P, c_int, c_int, P, P]),
-    "avs_hsv_frame_diff_batch_u8": (c_int, [P, c_int64, c_int, c_int, c_int, P, c_int, P, P]),
-    "avs_shot_cuts_batch": (c_int, [P, c_int64, P, c_int, c_double, c_double, c_int, P, P, P, P]),
-    "avs_shot_tables_fill": (c_int, [P, c_int, P, P, P, P, P, c_int64, P, P, c_int64, P, c_int64, P, P]),
-    "avs_gather_rows_u8": (c_int, [P, c_int64, c_int64, P, P, c_int64, P, P]),
-    "avs_shot_value_sums": (c_int, [P, c_int64, c_int, c_int64, P, c_int, P, P, c_int64, P, P]),
-    "avs_knapsack_batch_f64": (c_int, [P, c_int, c_int64, P, P, c_int, c_int, P, P, c_int64, P, c_int, P, P, P, P, P]),
-    "avs_mask_overlap_counts": (c_int, [P, P, c_int64, c_int, c_int64, P, c_int, P, P]),
-    "avs_resize_bilinear_gather2_u8": (c_int, [P, c_int64, c_int, c_int, P, c_int64, P, c_int, c_int, P, c_int, c_int, P]),
-    "avs_segment_mean_perm_f32": (c_int, [P, c_int64, c_int64, c_int, P, c_int64, P, c_int, P, c_int64, P]),
-    "avs_kts_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
-    "avs_kts_gram_f64": (c_int, [P, c_int64, c_int, c_int64, c_int64, P, c_int, P, c_int64, P, c_int64, P]),
-    "avs_kts_scatters_f64": (c_int, [P, P, c_int, c_int, P, c_size_t, c_int64, c_int64, c_int64, c_int64, P, P]),
-    "avs_kts_dp_f64": (c_int, [P, c_int, c_int, c_int, c_int64, c_int, P, P, c_size_t, c_int64, c_int64, c_int64, c_int64,
-                               c_int64, P, P, P, P, P, P, P, P]),
-}
+# name -> (restype, [argtypes]) of every entry point the header declares; every pointer but the descriptor's is an
+# address (c_void_p: a tensor's data_ptr(), byref(...), a ctypes array or None)
+_SIGNATURES = _HEADER.signatures({"avs_conv_desc": ConvDesc})
 
 _lib = None
 
 
 def declared_symbols():
-    """Names of every function include/avsum_hip.h declares (parsed from the header)."""
-    import re
-    text = open(HEADER_PATH).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(avs_[a-z0-9_]+)\s*\(", text)))
+    """Names of every function include/avsum_hip.h declares."""
+    return sorted(_HEADER.prototypes)
 
 
 def lib():
@@ -205,8 +92,9 @@ def lib():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args
-    if handle.avs_abi_version() != 5:
-        raise AvsError(f"ABI version mismatch: library reports {handle.avs_abi_version()}, binding expects 5")
+    if handle.avs_abi_version() != ABI_VERSION:
+        raise AvsError(f"ABI version mismatch: library reports {handle.avs_abi_version()}, the header says "
+                       f"{ABI_VERSION}")
     if STUDY and os.environ.get("AVS_TUNE_CONVBN_NARROW") is not None:
         handle.avs_tune_convbn_narrow(int(os.environ["AVS_TUNE_CONVBN_NARROW"]))
     if STUDY and os.environ.get("AVS_TUNE_PIPELINE") is not None:  # kernel-study override of the library default

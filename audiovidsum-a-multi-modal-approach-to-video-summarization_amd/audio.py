@@ -23,9 +23,11 @@ import numpy as np
 import torch
 
 from . import ops
+from ._header import load as _load_header
 
-N_FFT = 400
-HOP = 200
+_H = _load_header().constants     # the fused front end's sizes, shared with csrc/audio.hip (include/avsum_hip.h)
+N_FFT = _H["AVS_FUSED_NFFT"]    # 400
+HOP = _H["AVS_FUSED_HOP"]       # 200
 N_BINS = N_FFT // 2 + 1  # 201
 
 
@@ -68,9 +70,9 @@ def windowed_dft_basis():
     return np.concatenate([np.cos(ang) * window, -np.sin(ang) * window], 0)
 
 
-FUSED_COLS = 208      # 201 bins padded to 13 tiles of 16 (avs_stft_mel_fused_f32)
-FUSED_RE_ROWS = 204   # n = 0 .. 200 padded to a multiple of 4
-FUSED_IM_ROWS = 200   # n = 1 .. 199 padded to a multiple of 4
+FUSED_COLS = _H["AVS_FUSED_COLS"]         # 208: 201 bins padded to 13 tiles of 16 (avs_stft_mel_fused_f32)
+FUSED_RE_ROWS = _H["AVS_FUSED_RE_ROWS"]   # 204: n = 0 .. 200 padded to a multiple of 4
+FUSED_IM_ROWS = _H["AVS_FUSED_IM_ROWS"]   # 200: n = 1 .. 199 padded to a multiple of 4
 
 
 def folded_dft_tables():

@@ -191,13 +191,9 @@ extern "C" int avs_power_mel_f32(const float* d_spec, int64_t frames, int nbins,
 //     ascending bin order) and the log run on it, and only the [frames, n_mels] results are written.
 // Wave w: frames 16 (w & 1) .. + 15, column tiles 7 (w >> 1) .. of the 13 16-bin tiles (208 >= 201 bins).
 // ---------------------------------------------------------------------------
+// AVS_FUSED_NFFT, _HOP, _COLS, _RE_ROWS, _IM_ROWS (the shapes of the tables audio.py builds): include/avsum_hip.h
 #define AVS_FUSED_FPB 32
-#define AVS_FUSED_NFFT 400
-#define AVS_FUSED_HOP 200
 #define AVS_FUSED_BINS 201
-#define AVS_FUSED_COLS 208   // bins padded to 13 tiles of 16
-#define AVS_FUSED_RE_ROWS 204  // n = 0 .. 200 padded to a multiple of 4
-#define AVS_FUSED_IM_ROWS 200  // n = 1 .. 199 padded to a multiple of 4
 
 // SEG: a workgroup's frames come from a block table (first STFT frame, count <= 32, segment) instead of blockIdx * 32 and
 // nothing per frame is written: the block's per-mel SUMS over its frames (log2-mel, and the dB value clamped at
@@ -633,10 +629,7 @@ extern "C" int avs_stft_mel_shots_f32(const float* d_waves, int64_t waves_len, c
 // VGGish log-mel examples of a ragged batch: example e is 96 frames (window 400, hop 160, no padding) starting at sample
 // d_ex_start[e] of d_waves, samples clamped to [-1, 1] at load.  The same two kernels and the same per-frame arithmetic as
 // avs_stft_f64 + avs_power_mel_f32 mode 3 on a clamped slice (fp64 DFT, fp32 spectrum through the workspace).
-#define AVS_VGG_WINDOW 400
-#define AVS_VGG_HOP 160
-#define AVS_VGG_BINS 257
-#define AVS_VGG_FRAMES 96
+// AVS_VGG_WINDOW, _HOP, _BINS, _FRAMES (what vggish.py shapes its examples by): include/avsum_hip.h
 extern "C" int64_t avs_vggish_examples_workspace_bytes(int64_t nex) {
   if (nex < 0) return AVS_E_SHAPE;
   return nex * AVS_VGG_FRAMES * 2 * AVS_VGG_BINS * 4;   // the fp32 spectrum rows [nex * 96, 514]

@@ -10,10 +10,12 @@
 #define EM_BUF 8192      // elements numpy's reduction hands to its pairwise sum at a time
 #define EM_LEAF 128      // the pairwise sum's unrolled leaf (PW_BLOCKSIZE)
 #define EM_MAX_LEAVES 128  // a leaf below a split holds at least 64 elements, so a buffer has at most 8192 / 64 leaves
-#define EM_TILE 256      // rows of a video per workgroup of the pair-count kernel
-#define EM_CHUNK 1024    // columns staged through LDS per step
-#define EM_MAX_T 32768   // 4 T^4 < 2^63: every sum of the fold and the host's products fit int64
-#define EM_COLS 10       // int64 per video of the fold
+// the sizes ops.EvalTables shares (include/avsum_hip.h): rows of a video per workgroup of the pair-count kernel, columns
+// staged through LDS per step, the longest video, int64 per video of the fold
+#define EM_TILE AVS_EVAL_TILE
+#define EM_CHUNK AVS_EVAL_CHUNK
+#define EM_MAX_T AVS_EVAL_MAX_T
+#define EM_COLS AVS_EVAL_COLS
 
 // ---------------------------------------------------------------------------
 // Segment mean in numpy's order + mask.  One workgroup per segment.  np.mean of a contiguous vector sums buffers of

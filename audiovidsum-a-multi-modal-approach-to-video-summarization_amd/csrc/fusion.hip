@@ -65,7 +65,7 @@ extern "C" int avs_cdist_f64(const float* d_v, int tv, const float* d_a, int ta,
 // code of every cell goes to HBM.  A second one-thread kernel walks the codes
 // back from (n-1, m-1).  Tie order: up (i-1,j), left (i,j-1), diagonal.
 // ---------------------------------------------------------------------------
-#define DTW_MAX_N 6400  // 3 * 6400 * 8 B = 150 KiB of the 160 KiB LDS
+#define DTW_MAX_N AVS_FUSION_MAX_N  // 3 * 6400 * 8 B = 150 KiB of the 160 KiB LDS
 __global__ __launch_bounds__(1024) void dtw_sweep_kernel(const double* __restrict__ cost, int n, int m,
                                                          unsigned char* __restrict__ dir, double* __restrict__ total) {
   extern __shared__ double diag[];  // [3][n]

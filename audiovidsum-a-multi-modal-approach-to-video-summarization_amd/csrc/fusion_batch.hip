@@ -10,17 +10,18 @@
 #include "avs_internal.h"
 #include <math.h>
 
-#define FB_COLS 8        // int64 per pair-table row
-#define FB_MAX_N 6400    // as avs_dtw_path_f64: 3 * 6400 * 8 B = 150 KiB of the 160 KiB LDS
-#define FB_SMALL_L 64    // class 0: min(n, m) <= 64, one wave per pair, four pairs per workgroup
-#define FB_MID_L 512     // class 1: min(n, m) <= 512, one 256-thread workgroup per pair; above: 1024 threads
+// the sizes ops.FusionTables shares (include/avsum_hip.h)
+#define FB_COLS AVS_FUSION_PAIR_COLS  // int64 per pair-table row
+#define FB_MAX_N AVS_FUSION_MAX_N     // as avs_dtw_path_f64: 3 * 6400 * 8 B = 150 KiB of the 160 KiB LDS
+#define FB_SMALL_L AVS_FUSION_SMALL_L // class 0: min(n, m) <= 64, one wave per pair, four pairs per workgroup
+#define FB_MID_L AVS_FUSION_MID_L     // class 1: min(n, m) <= 512, one 256-thread workgroup per pair; above: 1024 threads
 
 // ---------------------------------------------------------------------------
 // Cost matrices.  One 16x16-thread block per entry of the (pair, row tile, column tile) table; the arithmetic and its
 // order are cdist_kernel's (float64 direct difference, k ascending in steps of 32, sqrt), so a pair's block is bit for
 // bit what avs_cdist_f64 gives for that pair.
 // ---------------------------------------------------------------------------
-#define CB_T 32
+#define CB_T AVS_FUSION_TILE
 #define CB_K 32
 __global__ __launch_bounds__(256) void cdist_batch_kernel(const float* __restrict__ v, const float* __restrict__ a, int d,
                                                           const int64_t* __restrict__ pairs,

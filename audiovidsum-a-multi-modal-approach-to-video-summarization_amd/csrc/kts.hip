@@ -12,14 +12,15 @@
 // The workspace: K1 | R | Jt (fp64) | p (uint16), each part starting at a multiple of 256 bytes.
 #include "avs_internal.h"
 
-#define KT_COLS 10
-#define KT_MAX_SAMPLES 2048
-#define KT_TILE 64                           // Gram tile: 4 waves x 16 rows, 4 column tiles of 16
+// the sizes ops.KtsTables shares (include/avsum_hip.h)
+#define KT_COLS AVS_KTS_VIDEO_COLS
+#define KT_MAX_SAMPLES AVS_KTS_MAX_SAMPLES
+#define KT_TILE AVS_KTS_TILE                 // Gram tile: 4 waves x 16 rows, 4 column tiles of 16
 #define KT_DP_THREADS 1024
 #define KT_DP_WAVES (KT_DP_THREADS / AVS_WAVE)
 #define KT_DP_ROWS 4                         // values of l a wave works on side by side
 #define KT_JT_L 8                            // rows l of Jt per wave: the 64 bytes of R[t - 1][l - 1 ..] a lane reads
-#define KT_MAX_VIDEOS 65535
+#define KT_MAX_VIDEOS AVS_KTS_MAX_VIDEOS
 
 typedef double kt_f64x4 __attribute__((ext_vector_type(4)));
 

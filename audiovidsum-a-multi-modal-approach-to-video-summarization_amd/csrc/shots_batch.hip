@@ -11,9 +11,9 @@
 #define SB_MAX_GRID_X (0xffffffffll / SB_THREADS)
 #define SB_WORDS 64                   // mask words of one chunk: one per lane of the wave that walks them
 #define SB_CHUNK (SB_WORDS * 64)      // frames of one chunk
-#define SB_MAX_FRAMES 100             // features/extractors.py MAX_FRAMES
-#define SB_INTERVAL 3                 // FRAME_INTERVAL
-#define SB_MICRO 4                    // MICRO_BATCH
+#define SB_MAX_FRAMES AVS_SHOT_MAX_FRAMES   // features/extractors.py MAX_FRAMES (include/avsum_hip.h, as the next two)
+#define SB_INTERVAL AVS_SHOT_INTERVAL       // FRAME_INTERVAL
+#define SB_MICRO AVS_SHOT_MICRO_BATCH       // MICRO_BATCH
 
 // ---------------------------------------------------------------------------
 // 1. |dH|, |dS|, |dV| sums of every frame against the previous frame OF ITS VIDEO: the arithmetic of

@@ -12,8 +12,8 @@
 #define SM_SUM_THREADS 256                   // four waves, one (row, shot) each
 #define SM_KNAP_THREADS 1024
 #define SM_SHOT_CHUNK 1024                   // shots whose (weight, value) are staged in LDS at a time
-#define SM_CELLS 8192                        // capacity + 1 <= 8192: the two fp64 rows are 128 KiB of the CU's 160 KiB
-#define SM_MAX_CAPACITY (SM_CELLS - 1)
+#define SM_MAX_CAPACITY AVS_SUMMARY_MAX_CAPACITY   // what ops.SummaryTables refuses above (include/avsum_hip.h)
+#define SM_CELLS (SM_MAX_CAPACITY + 1)       // the two fp64 rows of capacity + 1 cells are 128 KiB of the CU's 160 KiB
 #define SM_OV_THREADS 256
 #define SM_MAX_GRID_Y 65535
 

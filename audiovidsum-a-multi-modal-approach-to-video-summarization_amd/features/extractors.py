@@ -20,9 +20,10 @@ from ..audio import MelPlan
 from ..cnn import InceptionV3Runner, Inception3, ResNet50Runner, RESNET_MEAN, RESNET_STD, resnet50_trunk
 from ..vggish import VGGish
 
-FRAME_INTERVAL = 3  # extractors.py:399
-MAX_FRAMES = 100    # extractors.py:400
-MICRO_BATCH = 4     # extractors.py:48
+# the reference's sampling rule, which the batched shot kernels share (include/avsum_hip.h)
+FRAME_INTERVAL = ops.SHOT_INTERVAL   # 3: extractors.py:399
+MAX_FRAMES = ops.SHOT_MAX_FRAMES     # 100: extractors.py:400
+MICRO_BATCH = ops.SHOT_MICRO_BATCH   # 4: extractors.py:48
 
 
 def _device():

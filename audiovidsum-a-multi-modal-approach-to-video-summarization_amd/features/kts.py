@@ -32,7 +32,9 @@ kept gives the same result.  The published lmax is not offered (its default neve
 The host functions are pure numpy and importable without torch and without the kernel library."""
 import numpy as np
 
-KTS_MAX_SAMPLES = 2048
+from .._header import load as _load_header     # (re and ctypes only: still no torch, no kernel library)
+
+KTS_MAX_SAMPLES = _load_header().constants["AVS_KTS_MAX_SAMPLES"]   # 2048, shared with csrc/kts.hip
 
 
 def kts_penalties(n, m_max, vmax=1.0):

@@ -11,7 +11,7 @@ import torch
 from . import _abi
 from ._abi import (ACT_NONE, ACT_RELU, AVS_BF16, AVS_F16X2, AVS_F32, AVS_F32_SPLIT, BIAS_COL, BIAS_NONE, BIAS_ROW, check,
                    lib)
-from .ragged import (EVAL_CHUNK, EVAL_MAX_T, EVAL_TILE, FUSION_MAX_N, FUSION_MID_L, FUSION_SMALL_L,  # noqa: F401
+from .ragged import (EVAL_CHUNK, EVAL_COLS, EVAL_MAX_T, EVAL_TILE, FUSION_MAX_N, FUSION_MID_L, FUSION_SMALL_L,  # noqa: F401
                      KTS_MAX_SAMPLES, SHOT_INTERVAL, SHOT_MAX_FRAMES, SHOT_MICRO_BATCH, SUMMARY_MAX_CAPACITY, SUMMARY_MAX_ROWS,
                      EvalTables, FusionTables, KtsTables, RaggedOffsets, SeqTable, ShotTables, StageOneTables,
                      SummaryTables)
@@ -1027,10 +1027,12 @@ def stft_mel_fused(wave, window, cos_t, sin_t, fb, fb_lo, fb_hi, log2=False, db=
         raise ValueError("wave must be a contiguous 1-D tensor")
     if window.dtype != torch.float64 or cos_t.dtype != torch.float64 or sin_t.dtype != torch.float64:
         raise TypeError("window and DFT tables must be float64")
-    if tuple(cos_t.shape) != (204, 208) or tuple(sin_t.shape) != (200, 208) or window.numel() != 400:
+    c = _abi.SHARED
+    if (tuple(cos_t.shape) != (c["AVS_FUSED_RE_ROWS"], c["AVS_FUSED_COLS"]) or window.numel() != c["AVS_FUSED_NFFT"]
+            or tuple(sin_t.shape) != (c["AVS_FUSED_IM_ROWS"], c["AVS_FUSED_COLS"])):
         raise ValueError("tables must be cos [204, 208], -sin [200, 208], window [400]")
     t = wave.numel()
-    frames = 1 + t // 200
+    frames = 1 + t // c["AVS_FUSED_HOP"]
     nmel = fb.shape[1]
     mk = lambda on: torch.empty((frames, nmel), dtype=torch.float32, device=wave.device) if on else None
     o_log2, o_db, o_pow = mk(log2), mk(db), mk(power)
@@ -1159,10 +1161,10 @@ def vggish_examples(waves, ex_start, basis_t, fb, fb_lo, fb_hi):
     give for the clamped samples."""
     _dev(waves, ex_start, basis_t, fb)
     _f32(waves, "waves")
-    if basis_t.dtype != torch.float64 or not basis_t.is_contiguous() or basis_t.shape[0] != 400:
+    if basis_t.dtype != torch.float64 or not basis_t.is_contiguous() or basis_t.shape[0] != _abi.SHARED["AVS_VGG_WINDOW"]:
         raise ValueError("basis_t must be contiguous float64 [400, ncols_pad]")
     nex, nmel = ex_start.numel(), fb.shape[1]
-    out = torch.empty((nex, 96, nmel), dtype=torch.float32, device=waves.device)
+    out = torch.empty((nex, _abi.SHARED["AVS_VGG_FRAMES"], nmel), dtype=torch.float32, device=waves.device)
     if nex == 0:
         return out
     need = int(lib().avs_vggish_examples_workspace_bytes(nex))
@@ -1543,6 +1545,7 @@ def fusion_batch(tables, v, a, target_length=None, keep_cost=False):
 
 # --------------------------------------------------------------------------- batched evaluation
 EVAL_COLUMNS = ("T", "n_pred", "n_tgt", "tp", "S2", "E_x", "E_y", "S_xy", "S_xx", "S_yy")
+assert len(EVAL_COLUMNS) == EVAL_COLS      # the row avs_eval_fold writes (AVS_EVAL_COLS of include/avsum_hip.h)
 _EVAL_DTYPES = {torch.float32: 4, torch.float64: 8}
 
 
@@ -1589,7 +1592,7 @@ def eval_counts(tables, pred, target):
     if rows >= 1 << 31:
         raise ValueError(f"eval_counts: {rows} rows, the kernels index rows below 2^31")
     dev, nv = pred.device, tables.nvideos
-    out = torch.empty((nv, len(EVAL_COLUMNS)), dtype=torch.int64, device=dev)
+    out = torch.empty((nv, EVAL_COLS), dtype=torch.int64, device=dev)
     if nv == 0:
         return out
     mask_x = torch.empty(rows, dtype=torch.uint8, device=dev)

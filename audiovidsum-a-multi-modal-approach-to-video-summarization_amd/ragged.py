@@ -6,29 +6,36 @@ Pure host code on numpy and torch: nothing here touches the kernel library, so t
 import numpy as np
 import torch
 
+from ._header import load as _load_header
 from .features.kts import KTS_MAX_SAMPLES, kts_penalties   # (pure numpy: the limit and the penalty of the definitions)
 
-FUSION_MAX_N = 6400      # rows of the visual side of one pair (the per-pair limit of dtw_path)
-FUSION_SMALL_L = 64      # size classes by l = min(n, m): l <= 64 one wave per pair (four pairs per workgroup),
-FUSION_MID_L = 512       # l <= 512 one 256-thread workgroup per pair, above that one 1024-thread workgroup
-_FUSION_TILE = 32        # the cost kernel's output tile
+# The sizes the tables below share with the kernels that read them are the header's (include/avsum_hip.h, where each is
+# described), never a second copy.
+_H = _load_header().constants
+FUSION_MAX_N = _H["AVS_FUSION_MAX_N"]        # 6400: rows of the visual side of one pair (the per-pair limit of dtw_path)
+FUSION_SMALL_L = _H["AVS_FUSION_SMALL_L"]    # 64, 512: size classes by l = min(n, m) - one wave per pair (four pairs per
+FUSION_MID_L = _H["AVS_FUSION_MID_L"]        # workgroup), one 256-thread workgroup per pair, above that 1024 threads
+_FUSION_TILE = _H["AVS_FUSION_TILE"]         # 32: the cost kernel's output tile
+_FUSION_PAIR_COLS = _H["AVS_FUSION_PAIR_COLS"]   # 8: int64 per row of the pair table
 
-EVAL_MAX_T = 32768       # rows of one video: 4 T^4 < 2^63, so the fold's sums and the host's products fit int64
-EVAL_TILE = 256          # rows of a video per workgroup of the pair-count kernel
-EVAL_CHUNK = 1024        # columns it stages through LDS per step
+EVAL_MAX_T = _H["AVS_EVAL_MAX_T"]            # 32768: rows of one video
+EVAL_TILE = _H["AVS_EVAL_TILE"]              # 256: rows of a video per workgroup of the pair-count kernel
+EVAL_CHUNK = _H["AVS_EVAL_CHUNK"]            # 1024: columns it stages through LDS per step
+EVAL_COLS = _H["AVS_EVAL_COLS"]              # 10: int64 per video of the fold (ops.EVAL_COLUMNS names them)
 
-SHOT_INTERVAL = 3        # features/extractors.py FRAME_INTERVAL: the sampled frames are the multiples of 3,
-SHOT_MAX_FRAMES = 100    # MAX_FRAMES: at most 100 per shot,
-SHOT_MICRO_BATCH = 4     # MICRO_BATCH: in BatchNorm groups of 4 with a shorter tail group
+SHOT_INTERVAL = _H["AVS_SHOT_INTERVAL"]      # 3 (features/extractors.py FRAME_INTERVAL): the sampled frames are its multiples,
+SHOT_MAX_FRAMES = _H["AVS_SHOT_MAX_FRAMES"]  # 100 (MAX_FRAMES): at most that many per shot,
+SHOT_MICRO_BATCH = _H["AVS_SHOT_MICRO_BATCH"]    # 4 (MICRO_BATCH): in BatchNorm groups of 4 with a shorter tail group
 
-SUMMARY_MAX_CAPACITY = 8191   # knapsack cells 0 .. capacity: two fp64 rows of 8192 cells are 128 KiB of a CU's 160 KiB LDS
+SUMMARY_MAX_CAPACITY = _H["AVS_SUMMARY_MAX_CAPACITY"]   # 8191: knapsack cells 0 .. capacity, both fp64 rows LDS-resident
 SUMMARY_MAX_ROWS = 1024       # score rows of one knapsack batch (grid y).  The take-bit workspace holds rows * shot_cap *
                               # words uint64 entries with words <= 128: below 2^31 for every shot_cap below 2^14 = 16 384
                               # at the full 1024 rows and 8191 cells; past that the wrapper refuses by take_words itself
 
 # KTS_MAX_SAMPLES (2048, from features/kts.py): samples of one video - the two fp64 rows of the dynamic programme live in LDS
-KTS_TILE = 64           # rows and columns of a Gram tile
-KTS_MAX_VIDEOS = 65535   # videos of one batch (a grid dimension)
+KTS_TILE = _H["AVS_KTS_TILE"]                # 64: rows and columns of a Gram tile
+KTS_MAX_VIDEOS = _H["AVS_KTS_MAX_VIDEOS"]    # 65535: videos of one batch (a grid dimension)
+_KTS_VIDEO_COLS = _H["AVS_KTS_VIDEO_COLS"]   # 10: int64 per row of the video table
 
 
 def exclusive_offsets(lengths):
@@ -352,7 +359,7 @@ class KtsTables(RaggedOffsets):
         self.penalties = np.concatenate([kts_penalties(nv, mm, vmax) for nv, mm in zip(self.n, self.m_max)])
         self.workspace_bytes = sum((int(b) + 255) & ~255 for b in (8 * self.k1_entries, 8 * self.k_entries,
                                                                    8 * self.jt_entries, 2 * self.p_entries))
-        self.videos = np.zeros((self.nvideos, 10), dtype=np.int64)
+        self.videos = np.zeros((self.nvideos, _KTS_VIDEO_COLS), dtype=np.int64)
         for col, x in enumerate((self.offsets[:-1], self.lengths, self.n, self.m_max, self.k_offsets[:-1],
                                  self.k1_offsets[:-1], self.jt_offsets[:-1], self.p_offsets[:-1], self.cost_offsets[:-1])):
             self.videos[:, col] = x
@@ -409,7 +416,7 @@ class FusionTables:
         self.tiles = np.stack([tp, k // tj[tp], k % tj[tp]], 1).astype(np.int32).reshape(-1, 3)
         self.row_pair_host = np.repeat(np.arange(npairs, dtype=np.int32), n)
         self.workspace_bytes = (self.cells + 255) & ~255     # avs_dtw_batch_workspace_bytes: one code byte per cell
-        table = np.zeros((npairs, 8), dtype=np.int64)
+        table = np.zeros((npairs, _FUSION_PAIR_COLS), dtype=np.int64)
         for col, x in enumerate((v0, n, a0, m, self.cell_off, self.path_off, self.row_off)):
             table[:, col] = x
         self.pairs, self.order_t, self.tiles_t, self.row_pair = _upload(device, table, self.order, self.tiles,

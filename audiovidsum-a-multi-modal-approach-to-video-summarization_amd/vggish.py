@@ -21,12 +21,14 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from ._header import load as _load_header
 
+_H = _load_header().constants     # the sizes avs_vggish_examples_f32 shares (include/avsum_hip.h)
 SAMPLE_RATE = 16000
-WINDOW, HOP, FFT_LEN = 400, 160, 512
-NUM_BINS, NUM_MEL = FFT_LEN // 2 + 1, 64
+WINDOW, HOP, FFT_LEN = _H["AVS_VGG_WINDOW"], _H["AVS_VGG_HOP"], 512   # 400, 160
+NUM_BINS, NUM_MEL = _H["AVS_VGG_BINS"], 64                            # 257 = FFT_LEN // 2 + 1
 MEL_MIN_HZ, MEL_MAX_HZ = 125.0, 7500.0
-EXAMPLE_FRAMES = 96
+EXAMPLE_FRAMES = _H["AVS_VGG_FRAMES"]                                 # 96
 QUANT_MIN, QUANT_MAX = -2.0, 2.0
 
 

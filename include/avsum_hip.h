@@ -41,6 +41,44 @@ extern "C" {
 
 #define AVS_ABI_VERSION 5
 
+/* ---- sizes the host and the kernels share ---------------------------------
+ * The host builds tables that the kernels index by these numbers, shapes buffers by them and refuses what exceeds
+ * them.  Each is defined HERE and nowhere else: the kernel files use these names, and the Python host reads the
+ * values from this header (_header.py), as it reads the prototypes, the enums and avs_conv_desc.               */
+/* batched fusion (avs_cdist_batch_f64, avs_dtw_batch_f64; AVS_FUSION_MAX_N also avs_dtw_path_f64) */
+#define AVS_FUSION_MAX_N 6400      /* visual rows n of a pair: 3 anti-diagonals of fp64 = 150 KiB of the 160 KiB LDS */
+#define AVS_FUSION_SMALL_L 64      /* l = min(n, m) <= this: one wave per pair, four pairs per workgroup             */
+#define AVS_FUSION_MID_L 512       /* l <= this: one 256-thread workgroup per pair; above: 1024 threads              */
+#define AVS_FUSION_TILE 32         /* rows and columns of a cost tile of d_tiles                                     */
+#define AVS_FUSION_PAIR_COLS 8     /* int64 per row of d_pairs                                                       */
+/* batched evaluation (avs_rank_pair_counts, avs_eval_fold) */
+#define AVS_EVAL_MAX_T 32768       /* rows of a video: 4 T^4 < 2^63, the fold's sums and the host's products fit int64 */
+#define AVS_EVAL_TILE 256          /* rows of a video per entry of d_tiles                                           */
+#define AVS_EVAL_CHUNK 1024        /* columns the pair-count kernel stages through LDS per step                      */
+#define AVS_EVAL_COLS 10           /* int64 per video of avs_eval_fold's d_out                                       */
+/* batched shot detection and frame sampling (avs_shot_cuts_batch, avs_shot_tables_fill; features/extractors.py) */
+#define AVS_SHOT_INTERVAL 3        /* the sampled frames of a shot are the multiples of this                         */
+#define AVS_SHOT_MAX_FRAMES 100    /* at most this many per shot                                                     */
+#define AVS_SHOT_MICRO_BATCH 4     /* in BatchNorm groups of this many, with a shorter tail group                    */
+/* keyshot summaries (avs_knapsack_batch_f64) */
+#define AVS_SUMMARY_MAX_CAPACITY 8191  /* cells 0 .. capacity: two fp64 rows of 8192 cells = 128 KiB of the LDS      */
+/* kernel temporal segmentation (avs_kts_*) */
+#define AVS_KTS_MAX_SAMPLES 2048   /* samples n of a video: both live fp64 rows of the programme stay in LDS         */
+#define AVS_KTS_TILE 64            /* rows and columns of a Gram tile of d_tiles                                     */
+#define AVS_KTS_MAX_VIDEOS 65535   /* videos of a batch (a grid dimension)                                           */
+#define AVS_KTS_VIDEO_COLS 10      /* int64 per row of d_videos                                                      */
+/* the fused mel front end (avs_stft_mel_fused_f32 and the kernels built on it): the shapes of d_window, d_cos, d_sin */
+#define AVS_FUSED_NFFT 400
+#define AVS_FUSED_HOP 200
+#define AVS_FUSED_COLS 208         /* the 201 bins padded to 13 tiles of 16                                          */
+#define AVS_FUSED_RE_ROWS 204      /* n = 0 .. 200 padded to a multiple of 4                                         */
+#define AVS_FUSED_IM_ROWS 200      /* n = 1 .. 199 padded to a multiple of 4                                         */
+/* VGGish examples (avs_vggish_examples_f32) */
+#define AVS_VGG_WINDOW 400         /* samples of a frame                                                             */
+#define AVS_VGG_HOP 160
+#define AVS_VGG_BINS 257           /* re | im columns of d_basis_t each, rows of d_fb                                */
+#define AVS_VGG_FRAMES 96          /* frames of an example                                                           */
+
 enum {
   AVS_OK = 0,
   AVS_E_ARG = -1,       /* null pointer / bad enum / negative size            */
@@ -491,8 +529,8 @@ int avs_stft_f64(const float* d_xpad, int64_t xpad_len, int64_t frames, int hop,
  *   d_log2mel = log2(mel + 1e-6)   (:245),   d_db = 10 log10(max(mel, 1e-10))   (AmplitudeToDB before its top_db
  *   clamp; d_max receives max(max(mel, 1e-10)) over the call for avs_clamp_topdb_f32; zero it first),   d_power = mel.
  * A workgroup stages the waveform span of its 32 frames in LDS (reflect padding by index, 16-byte loads), runs the
- * real DFT folded to half its length (d_window = the fp32 window values as float64 [400]; d_cos [204, 208] / d_sin
- * [200, 208] = cos / -sin(2 pi k n / 400), float64) on the fp64 matrix cores, then |X|^2, the sparse mel sum
+ * real DFT folded to half its length (d_window = the fp32 window values as float64 [AVS_FUSED_NFFT]; d_cos
+ * [AVS_FUSED_RE_ROWS, AVS_FUSED_COLS] / d_sin [AVS_FUSED_IM_ROWS, AVS_FUSED_COLS] = cos / -sin(2 pi k n / 400), float64) on the fp64 matrix cores, then |X|^2, the sparse mel sum
  * (d_fb [201, nmel], filter m non-zero on bins d_fb_lo[m] .. d_fb_hi[m] - 1) and the log on chip: the spectrum
  * never reaches HBM.  Replaces avs_reflect_pad_f32 + avs_stft_f64 + avs_power_mel_f32 for this front end.          */
 int avs_stft_mel_fused_f32(const float* d_wave, int64_t t, const double* d_window, const double* d_cos,
@@ -552,11 +590,11 @@ int avs_stft_mel_shots_f32(const float* d_waves, int64_t waves_len, const int64_
                            float top_db, float* d_mean_log2, int64_t ld_log2, float* d_mean_db, int64_t ld_db, void* d_ws,
                            int64_t ws_bytes, avs_stream_t stream);
 
-/* VGGish log-mel examples of a ragged batch (vggish_input.waveform_to_examples per shot): example e = 96 frames of 400
- * samples at hop 160 (no padding) starting at sample d_ex_start[e] (int64 [nex]) of d_waves (waves_len samples; a start
+/* VGGish log-mel examples of a ragged batch (vggish_input.waveform_to_examples per shot): example e = AVS_VGG_FRAMES (96)
+ * frames of AVS_VGG_WINDOW (400) samples at hop AVS_VGG_HOP (160) (no padding) starting at sample d_ex_start[e] (int64 [nex]) of d_waves (waves_len samples; a start
  * is clamped on the device into [0, waves_len - 15600]), each sample clamped to [-1, 1] at load.  d_out fp32 [nex, 96,
- * nmel] = ln(|STFT| . mel + 0.01); d_basis_t as avs_stft_f64 ([400, ncols_pad] float64, 257 re | 257 im columns),
- * d_fb [257, nmel] as avs_power_mel_f32.  Two launches (the fp64 DFT into the workspace, then avs_power_mel_f32 mode 3's
+ * nmel] = ln(|STFT| . mel + 0.01); d_basis_t as avs_stft_f64 ([AVS_VGG_WINDOW, ncols_pad] float64, AVS_VGG_BINS (257) re | as
+ * many im columns), d_fb [AVS_VGG_BINS, nmel] as avs_power_mel_f32.  Two launches (the fp64 DFT into the workspace, then avs_power_mel_f32 mode 3's
  * kernel): the per-frame arithmetic of avs_stft_f64 + avs_power_mel_f32 mode 3, so the examples are bit-identical to those
  * of a clamped slice.  d_ws: avs_vggish_examples_workspace_bytes(nex) bytes.  nex = 0: no launch.                      */
 int64_t avs_vggish_examples_workspace_bytes(int64_t nex);
@@ -724,7 +762,7 @@ int avs_cdist_f64(const float* d_v, int tv, const float* d_a, int ta, int d,
  * A.9): D = C + min(up, left, diag) with tie order up, left, diag; path from
  * (0,0) to (n-1,m-1) written as int64 pairs to d_path (capacity n+m-1 pairs),
  * its length to *d_path_len, total cost to *d_cost.  The three live
- * anti-diagonals stay in LDS (n <= 6400); the workspace holds one predecessor
+ * anti-diagonals stay in LDS (n <= AVS_FUSION_MAX_N); the workspace holds one predecessor
  * byte per cell.                                                            */
 int64_t avs_dtw_workspace_bytes(int n, int m);
 int avs_dtw_path_f64(const double* d_cost_matrix, int n, int m, void* d_workspace,
@@ -737,7 +775,7 @@ int avs_gather_scale_f32(const float* d_x, int64_t ldx, int d, const int64_t* d_
                          avs_stream_t stream);
 
 /* ---- batched fusion: P ragged (visual [n_p,D], audio [m_p,D]) pairs per call, a fixed number of launches ----------
- * The pairs are row ranges of two row-major fp32 matrices; nothing is padded.  d_pairs is int64 [npairs, 8] =
+ * The pairs are row ranges of two row-major fp32 matrices; nothing is padded.  d_pairs is int64 [npairs, AVS_FUSION_PAIR_COLS] =
  * (v_row0, n, a_row0, m, cell_off, path_off, row_off, 0): cell_off = first element of the pair's row-major [n, m]
  * block in the cost buffer (doubles) and in the code workspace (bytes), path_off = first row of its path slot
  * (capacity n + m - 1 rows), row_off = first of its n row counts.  The tables are trusted: the caller (ops.FusionTables)
@@ -745,15 +783,16 @@ int avs_gather_scale_f32(const float* d_x, int64_t ldx, int d, const int64_t* d_
  * point synchronises or reads a result back.                                                                        */
 
 /* Every pair's cost matrix, bit for bit avs_cdist_f64 of that pair.  d_tiles is int32 [ntiles, 3] = (pair, row tile,
- * column tile) over 32x32 tiles; cells = the sum of n*m.                                                            */
+ * column tile) over tiles of AVS_FUSION_TILE rows and columns; cells = the sum of n*m.                              */
 int avs_cdist_batch_f64(const float* d_v, int64_t v_rows, const float* d_a, int64_t a_rows, int d,
                         const int64_t* d_pairs, int npairs, const int32_t* d_tiles, int64_t ntiles, double* d_cost,
                         int64_t cells, avs_stream_t stream);
 
 /* Exact DTW of every pair (recurrence and tie order of avs_dtw_path_f64) + backtrack.  d_order is int32 [npairs]: the
- * pairs sorted into three size classes by l = min(n, m): the first n_small have l <= 64 (one wave per pair, four
- * pairs per workgroup), the next n_mid 64 < l <= 512 (256 threads per pair), the last n_large l > 512 (1024 threads);
- * max_l_* is the largest l of each class (it sizes that launch's LDS) and max_n the largest n (<= 6400).  One launch
+ * pairs sorted into three size classes by l = min(n, m): the first n_small have l <= AVS_FUSION_SMALL_L (one wave per
+ * pair, four pairs per workgroup), the next n_mid AVS_FUSION_SMALL_L < l <= AVS_FUSION_MID_L (256 threads per pair), the
+ * last n_large l > AVS_FUSION_MID_L (1024 threads); max_l_* is the largest l of each class (it sizes that launch's LDS)
+ * and max_n the largest n (<= AVS_FUSION_MAX_N).  One launch
  * per non-empty class.  Per pair: the path (int64 pairs, start to end) into its slot of d_path, d_path_len[p],
  * d_total[p], and d_rowcount[row_off + i] = the number of path cells in row i.  The workspace holds one predecessor
  * byte per cell.                                                                                                     */
@@ -789,14 +828,15 @@ int avs_segment_mean_mask(const void* d_x, int elem_bytes, int64_t rows, const i
 /* Per row i of every video, over all j of the same video: d_counts int32 [5, rows] = planes (#{x_j < x_i},
  * #{x_j == x_i} self included, the same two on y, sum_j sign(x_i - x_j) sign(y_i - y_j)), x = d_pred (float32),
  * y = d_target (target_bytes 4 = float32, 8 = float64).  IEEE comparisons (-0.0 == 0.0); the inputs must be finite.
- * d_tiles is int32 [ntiles, 2] = (video, row tile) over tiles of 256 rows; max_t = the longest video (<= 32768).      */
+ * d_tiles is int32 [ntiles, 2] = (video, row tile) over tiles of AVS_EVAL_TILE rows; max_t = the longest video
+ * (<= AVS_EVAL_MAX_T).                                                                                               */
 int avs_rank_pair_counts(const float* d_pred, const void* d_target, int target_bytes, int64_t rows,
                          const int64_t* d_offsets, int nseg, const int32_t* d_tiles, int64_t ntiles, int max_t,
                          int32_t* d_counts, avs_stream_t stream);
 
-/* d_out int64 [nseg, 10] = (T, n_pred, n_tgt, tp, S2, E_x, E_y, S_xy, S_xx, S_yy) per video: the mask sums and their
+/* d_out int64 [nseg, AVS_EVAL_COLS] = (T, n_pred, n_tgt, tp, S2, E_x, E_y, S_xy, S_xx, S_yy) per video: the mask sums and their
  * overlap, S2 = sum s = 2 (concordant - discordant), E = sum eq (tied pairs = (E - T) / 2), and the sums of products
- * of the doubled average ranks 2r = 2 less + eq + 1.  With T <= 32768 every sum, and T * S_xy on the host, fits int64. */
+ * of the doubled average ranks 2r = 2 less + eq + 1.  With T <= AVS_EVAL_MAX_T every sum, and T * S_xy on the host, fits int64. */
 int avs_eval_fold(const int32_t* d_counts, const uint8_t* d_mask_pred, const uint8_t* d_mask_target, int64_t rows,
                   const int64_t* d_offsets, int nseg, int max_t, int64_t* d_out, avs_stream_t stream);
 
@@ -845,8 +885,9 @@ int avs_hsv_frame_diff_batch_u8(const uint8_t* d_frames, int64_t n, int h, int w
  * before the first).  Video v's cuts (video-relative frames, ascending) go to d_cuts[d_cut_off[v] ...]; d_cut_off is
  * int64 [nvideos + 1], the exclusive scan of the slot sizes (n_v - 1) / min_scene_len - the most the rule can place.
  * The rest of a slot is not written; a slot that is full ends the video's cuts (no store leaves the slot).
- * d_totals int64 [nvideos, 4] = (shots: 0 without a cut, else cuts + 1; sampled frames; micro-batch groups of 4; the
- * most sampled frames of one shot), a shot (s, e) holding min(100, ceil(e/3) - ceil(s/3)) sampled frames.             */
+ * d_totals int64 [nvideos, 4] = (shots: 0 without a cut, else cuts + 1; sampled frames; micro-batch groups of
+ * AVS_SHOT_MICRO_BATCH; the most sampled frames of one shot), a shot (s, e) holding min(AVS_SHOT_MAX_FRAMES, ceil(e/i) -
+ * ceil(s/i)) sampled frames, i = AVS_SHOT_INTERVAL.                                                                  */
 int avs_shot_cuts_batch(const uint32_t* d_sums, int64_t n, const int64_t* d_offsets, int nvideos, double pixels,
                         double threshold, int min_scene_len, const int64_t* d_cut_off, int64_t* d_cuts,
                         int64_t* d_totals, avs_stream_t stream);
@@ -855,8 +896,8 @@ int avs_shot_cuts_batch(const uint32_t* d_sums, int64_t n, const int64_t* d_offs
  * d_video_off int64 [3, nvideos + 1]: the exclusive scans of (shots, sampled frames, groups) per video; plane 0 is the
  * shot_offsets table.  d_shots int64 [S, 2]: video-relative (start, end).  d_sample_offsets int64 [S + 1]: first row
  * of each shot in the sampled tensor.  d_sample_index int64 [F]: rows of the concatenated frames, frame k of shot
- * (s, e) of video v being offsets[v] + 3 (ceil(s/3) + k).  d_group_offsets int64 [G + 1]: rows of the sampled tensor,
- * each shot cut into groups of 4 with a shorter tail group.  d_counts int64 [4] = (S, F, G, most frames of a shot).
+ * (s, e) of video v being offsets[v] + i (ceil(s/i) + k), i = AVS_SHOT_INTERVAL.  d_group_offsets int64 [G + 1]: rows of
+ * the sampled tensor, each shot cut into groups of AVS_SHOT_MICRO_BATCH with a shorter tail group.  d_counts int64 [4] = (S, F, G, most frames of a shot).
  * The capacities are those of the buffers (S + 1 <= shot_cap + 1 entries of d_sample_offsets, ...); nothing is written
  * past them.                                                                                                          */
 int avs_shot_tables_fill(const int64_t* d_offsets, int nvideos, const int64_t* d_cut_off, const int64_t* d_cuts,
@@ -887,7 +928,8 @@ int avs_shot_value_sums(const float* d_scores, int64_t ld_scores, int nrows, int
                         int64_t* d_sums, avs_stream_t stream);
 
 /* One 0/1 knapsack per (k, v), one workgroup of 1024 threads each: shot i of video v has weight w_i = end - start and
- * value double(sum_i) / double(w_i); the capacity is d_capacity[v] (int64 [nvideos], at most max_capacity <= 8191).
+ * value double(sum_i) / double(w_i); the capacity is d_capacity[v] (int64 [nvideos], at most max_capacity <=
+ * AVS_SUMMARY_MAX_CAPACITY).
  * row[w] = max over "skip" and, where w >= w_i, row'[w - w_i] + value, the shot TAKEN only where that is strictly
  * greater; both fp64 rows live in LDS (128 KiB of a CU's 160 KiB).  The take bits of shot g =
  * d_shot_offsets[v] + i are written as uint64 words (bit w & 63 of word w >> 6) to d_take [nrows][shot_cap][words],
@@ -930,17 +972,17 @@ int avs_segment_mean_perm_f32(const float* d_x, int64_t ldx, int64_t x_rows, int
                               avs_stream_t stream);
 
 /* ---- kernel temporal segmentation of a ragged batch (csrc/kts.hip; the definitions: features/kts.py) ----------------
- * The host plan (ops.KtsTables) gives d_videos int64 [nvideos][10] = per video (first feature row, frames N, samples
- * n = ceil(N / stride) <= 2048, m_max, first entry of its block in the packed K / R buffers [n][n], in K1 [n + 1], in
+ * The host plan (ops.KtsTables) gives d_videos int64 [nvideos][AVS_KTS_VIDEO_COLS] = per video (first feature row, frames
+ * N, samples n = ceil(N / stride) <= AVS_KTS_MAX_SAMPLES, m_max, first entry of its block in the packed K / R buffers [n][n], in K1 [n + 1], in
  * Jt [n + 1][n + 1], in p [m_max + 1][n + 1], in the cost / change-point / shot slots [m_max + 1], 0) and the packed
  * sizes: k1_entries, k_entries, jt_entries, p_entries, cost_cap, each below 2^31.  The table is trusted.  The workspace
  * holds K1 | R | Jt (fp64) | p (uint16), each part at a multiple of 256 bytes: avs_kts_workspace_bytes (0 for sizes out
- * of range).  nvideos <= 65535.  No atomics; no kernel waits on another workgroup; nothing allocates or synchronises. */
+ * of range).  nvideos <= AVS_KTS_MAX_VIDEOS.  No atomics; no kernel waits on another workgroup; nothing allocates or synchronises. */
 size_t avs_kts_workspace_bytes(int64_t k1_entries, int64_t k_entries, int64_t jt_entries, int64_t p_entries);
 
 /* d_gram[k_off_v + i * n + j] = sum over c < d of double(x_i[c]) * double(x_j[c]) on v_mfma_f64_16x16x4_f64, x_i = row
  * first_row_v + i * stride of d_x fp32 [rows, d] with row pitch ld >= d (4-byte alignment suffices; read in place).
- * d_tiles int32 [ntiles][3] = (video, ti, tj) with ti <= tj: the 64 x 64 tiles of the upper triangles.  The elements
+ * d_tiles int32 [ntiles][3] = (video, ti, tj) with ti <= tj: the AVS_KTS_TILE x AVS_KTS_TILE tiles of the upper triangles.  The elements
  * i <= j are stored to [i][j] and [j][i] from one register: K is symmetric to the bit, and a video's block does not
  * depend on the batch around it.                                                                                      */
 int avs_kts_gram_f64(const float* d_x, int64_t rows, int d, int64_t ld, int64_t stride, const int64_t* d_videos,
