@@ -7,8 +7,9 @@
 // group for a slab of output channels and walks them twice:
 //   pass 1  tiles of 128 rows x BN channels on the matrix cores, only column sums / sums of squares kept
 //           (registers -> one shuffle -> LDS across the two row-waves): deterministic, no atomics;
-//   pass 2  the same tiles again (operands now come from L2), epilogue = scale/shift from pass 1,
-//           residual add, ReLU, bf16, LDS-staged 16-byte stores of the FINAL activations.
+//   pass 2  the same tiles again (operands now come from L2), epilogue = t = bf16(fma(acc, scale, shift)) with the
+//           scale/shift of pass 1, staged in LDS; with a residual the sum is rounded a SECOND time, bf16(t + r)
+//           (r = res, or res * res_scale + res_shift); ReLU last; 16-byte stores of the FINAL activations.
 // HBM per element: one write (+ one residual read).  The second pass doubles the matrix work of
 // layers whose cost is their memory traffic, not their FLOPs.
 //
@@ -363,9 +364,9 @@ static int conv1x1_bn_launch(const char* who, const void* d_x, int64_t lin_strid
   const bool pre = d_pre_scale != nullptr;
   AVS_REQUIRE(d_x && d_w && d_y && (pre ? d_pre_shift != nullptr : (d_gamma && d_beta)), AVS_E_ARG, "%s: null pointer",
               who);
-  AVS_REQUIRE(k % 8 == 0 && n % 8 == 0 && lin_stride % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && ldb >= k &&
-                  ldc >= n && (!d_residual || (ldr % 8 == 0 && ldr >= n)),
-              AVS_E_SHAPE, "%s: k, n and every stride must be multiples of 8 elements (16 bytes)", who);
+  AVS_REQUIRE(k % 8 == 0 && n % 8 == 0 && lin_stride % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && lin_stride >= k &&
+                  ldb >= k && ldc >= n && (!d_residual || (ldr % 8 == 0 && ldr >= n)),
+              AVS_E_SHAPE, "%s: k, n and every stride must be multiples of 8 elements (16 bytes), no stride below its row", who);
   AVS_REQUIRE(avs_aligned16(d_x) && avs_aligned16(d_w) && avs_aligned16(d_y) && avs_aligned16(d_residual),
               AVS_E_ALIGN, "%s: operands must be 16-byte aligned", who);
   const bool ra = d_res_scale != nullptr;

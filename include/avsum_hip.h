@@ -347,7 +347,7 @@ int avs_stem_conv_pool_f16x2(const uint8_t* d_frames, int n, const void* d_w, in
  * One workgroup owns a whole group for a slab of channels and walks it twice (statistics, then the
  * normalised output), so the raw convolution never goes to HBM: replaces avs_conv2d_nhwc_bnstats +
  * avs_bn_apply for the 1x1 layers of the train-mode ResNet trunk
- * (features/extractors.py:65).  x rows at stride lin_stride; k, n and strides multiples of 8 elements.    */
+ * (features/extractors.py:65).  x rows at stride lin_stride >= k; k, n and strides multiples of 8 elements. */
 int avs_conv1x1_bn_bf16(const void* d_x, int64_t lin_stride, int k, const void* d_w, int64_t ldb, int n,
                         int64_t rows_per_group, int groups, const float* d_gamma, const float* d_beta,
                         float eps, const void* d_residual, int64_t ldr, int relu, void* d_y, int64_t ldc,

@@ -41,7 +41,8 @@ No step failed: the runner's hand-offs are right.
 bf16 is NOT tested here.  Measured against the float64 trace: relative L2 6.2e-2 / 3.1e-2, 1 - cosine 1.9e-3 / 4.9e-4
 (fours / per-frame).  Bars of 3 times that (0.19, 0.09) are not 10 times below the planted mistakes in the same metric
 (relative L2 from 0.004 - one flipped sign in the last BatchNorm - to 0.17; test_trunk_f64_host.py), so the case could not
-tell a wiring mistake from bf16 rounding and was left out, as was any forced comparison of bf16 steps.
+tell a wiring mistake from bf16 rounding and was left out.  The bf16 convolution + BatchNorm kernels are held to float64
+one kernel at a time, per (group, channel), in test_gpu_convbn_f64.py.
 
 The folded cases run on dark frames (trunk_f64_inputs.frames): with synthetic running statistics the trunk does not
 normalise and full-range frames carry layer 4 to 2e6, past the 65504 at which AVS_F16X2 saturates by design.
