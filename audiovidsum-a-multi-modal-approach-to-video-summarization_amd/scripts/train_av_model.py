@@ -11,6 +11,10 @@ With torch.distributed initialised (one process per GPU) the gradients are all-r
 ``train_on_dataset(..., videos_per_step=k)`` with k in 2..8 trains on k of the eight videos the loader draws, as ONE ragged
 batch per optimiser step (``collate_videos`` -> ``train_step_batch``: AVBiLSTMModel.train_rows, ops.seq_mse, the mean
 of the per-video losses).  The default k = 1 is the reference's loop, untouched.
+
+``train_on_dataset(..., optimizer="fused")`` replaces torch.optim.AdamW by optim.FusedAdamW (libavsum_optim.so: the whole
+step in at most three launches, optionally with global-norm clipping and the skip of a non-finite step, both decided on
+the device).  The default "torch" is the reference's optimiser, untouched.
 """
 import torch
 import torch.nn.functional as F
@@ -93,7 +97,8 @@ def select_items(items, rank, world, videos_per_step):
     return [items[i] for i in picked]
 
 
-def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, device="cuda", videos_per_step=1):
+def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, device="cuda", videos_per_step=1,
+                     optimizer="torch", max_grad_norm=None, skip_nonfinite=False):
     """One process: the reference's loop exactly (its DataLoader, its global-RNG shuffle, item 0 of every batch of 8).
     With torch.distributed initialised (one process per GPU) it is data-parallel over that loop: rank 0's weights are
     broadcast first (C1), every rank draws the SAME shuffled batches of 8 (the shuffle seed comes from rank 0) and
@@ -103,8 +108,18 @@ def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, dev
     videos_per_step = k in 2..8: every optimiser step trains on k videos of the drawn batch of 8 as one ragged batch
     (train_step_batch) - positions (rank + j * world) % len(batch), j < k, duplicates dropped; k = 8 in one process
     uses every video the loader draws.  on_step then receives the mean of the step's per-video losses.  Dropout draws
-    its masks for the whole batch at once, so torch's RNG is consumed differently from k one-video steps."""
+    its masks for the whole batch at once, so torch's RNG is consumed differently from k one-video steps.
+
+    optimizer = "torch" (the default): torch.optim.AdamW, as the reference; max_grad_norm and skip_nonfinite must be
+    left unset.  optimizer = "fused": optim.FusedAdamW(lr=lr, max_grad_norm=..., skip_nonfinite=...), the same update
+    in fused HIP kernels; the model's ``fused_optimizer`` attribute then holds it (stats(), state_dict()).  In a
+    data-parallel run allreduce_gradients runs BEFORE step() (train_step, train_step_batch), so every rank sees the same
+    gradients, computes the same norm and takes the same skip decision: the replicas stay identical."""
     import torch.distributed as tdist
+    if optimizer not in ("torch", "fused"):
+        raise ValueError(f"optimizer must be 'torch' or 'fused', got {optimizer!r}")
+    if optimizer == "torch" and (max_grad_norm is not None or skip_nonfinite):
+        raise ValueError("max_grad_norm and skip_nonfinite need optimizer='fused'")
     if not isinstance(videos_per_step, int) or not 1 <= videos_per_step <= 8:
         raise ValueError(f"videos_per_step must be 1..8 (the loader draws batches of 8), got {videos_per_step!r}")
     model = (model or AVBiLSTMModel()).to(device)
@@ -120,7 +135,12 @@ def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, dev
     else:
         collate = lambda items: select_items(items, rank, world, videos_per_step)  # noqa: E731
     loader = DataLoader(dataset, batch_size=8, shuffle=True, generator=gen, collate_fn=collate)
-    optimizer = torch.optim.AdamW(model.parameters(), lr=lr)
+    if optimizer == "fused":
+        from ..optim import FusedAdamW
+        optimizer = FusedAdamW(model.parameters(), lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        model.fused_optimizer = optimizer
+    else:
+        optimizer = torch.optim.AdamW(model.parameters(), lr=lr)
     for _ in range(epochs):
         model.train()
         if videos_per_step == 1:
