@@ -55,31 +55,29 @@ class LaunchProfiler:
             return self._pool.pop()
         return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
-    def summary(self):
+    def _totals(self, key_of):
+        """{key: {"launches", "flops", "bytes", "ms"}} over the timed launches for which key_of(kind, dtype, form) is not
+        None."""
         torch.cuda.synchronize()
         out = {}
-        for kind, dt, flops, nbytes, s, e, _ in self.records:
-            d = out.setdefault((kind, dt), {"launches": 0, "flops": 0.0, "bytes": 0.0, "ms": 0.0})
+        for kind, dt, flops, nbytes, s, e, form in self.records:
+            key = key_of(kind, dt, form)
+            if key is None:
+                continue
+            d = out.setdefault(key, {"launches": 0, "flops": 0.0, "bytes": 0.0, "ms": 0.0})
             d["launches"] += 1
             d["flops"] += flops
             d["bytes"] += nbytes
             d["ms"] += s.elapsed_time(e)
         return out
 
+    def summary(self):
+        return self._totals(lambda kind, dt, form: (kind, dt))
+
     def forms(self, kind, dt):
         """The timed launches of one kind split by the FORM the wrapper tagged them with (epilogue form x filter size of
         the contraction kernel): {form: {"launches", "flops", "bytes", "ms"}}."""
-        torch.cuda.synchronize()
-        out = {}
-        for k, d_, flops, nbytes, s, e, form in self.records:
-            if k != kind or d_ != dt:
-                continue
-            d = out.setdefault(form or "other", {"launches": 0, "flops": 0.0, "bytes": 0.0, "ms": 0.0})
-            d["launches"] += 1
-            d["flops"] += flops
-            d["bytes"] += nbytes
-            d["ms"] += s.elapsed_time(e)
-        return out
+        return self._totals(lambda k, d, form: (form or "other") if (k, d) == (kind, dt) else None)
 
 
 _profiler = None
@@ -215,7 +213,10 @@ def _device_arg(t, name, what, dtypes=None, ndim=None, shape=None, numel=None, d
         raise ValueError(f"{what}: {name} must be a device tensor (there is no CPU fallback)")
     if dtypes is not None and t.dtype not in dtypes:
         raise ValueError(f"{what}: {name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
-    if shape is not None and (t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape))):
+    # (t.shape == shape settles a shape without free extents at once: this check runs before every launch of the
+    # convolution wrappers)
+    if shape is not None and t.shape != shape and (
+            t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape))):
         raise ValueError(f"{what}: {name} must have shape {list(shape)} (None: any), got {list(t.shape)}")
     if (ndim is not None and t.dim() != ndim) or (numel is not None and t.numel() != numel) or \
             (contiguous and not t.is_contiguous()):
@@ -239,6 +240,108 @@ def _tables_arg(tables, cls, what, device=None, rows=None):
     if rows is not None and tables.total != rows:
         raise ValueError(f"{what}: the offsets end at {tables.total}, the batch has {rows} rows")
     return tables
+
+
+def _group_affine(pair, name, what, groups, cols):
+    """The (scale, shift) of a per-group affine operand ``name`` of wrapper ``what``: each a contiguous fp32 device tensor
+    [groups, cols], or a ValueError that starts with ``what`` and names the operand.  The kernels read these as fp32
+    rows of ``cols`` entries whatever the tensor says, so every such operand goes through here."""
+    scale, shift = pair
+    for part, t in (("scale", scale), ("shift", shift)):
+        _device_arg(t, part if name is None else f"{name} {part}", what, dtypes=(torch.float32,), shape=(groups, cols))
+    return scale, shift
+
+
+def _res_affine(res_affine, residual, what, groups, cols):
+    """The (scale, shift) a raw-convolution-output residual is added through, (None, None) without one."""
+    if res_affine is None:
+        return None, None
+    if residual is None:
+        raise ValueError(f"{what}: res_affine without a residual")
+    return _group_affine(res_affine, "res_affine", what, groups, cols)
+
+
+def _ld(t):
+    """Leading dimension (row stride in elements) of an optional 2-D operand: 0 when it is absent."""
+    return 0 if t is None else t.stride(0)
+
+
+def _query(status, name, may_decline=True):
+    """What a host-only query of the library answered: None when it declines the shape (E_UNSUPPORTED; an AvsError
+    where the caller has nothing else to offer, may_decline=False), an AvsError for any other negative status, otherwise
+    the value."""
+    if status == _abi.E_UNSUPPORTED and may_decline:
+        return None
+    if status < 0:
+        check(int(status), name)
+    return int(status)
+
+
+# one buffer per (device, stream): launches on ONE stream are ordered, so consecutive layers can share it; two streams
+# must not
+def _ws_key(device):
+    return (device, torch.cuda.current_stream(device).cuda_stream)
+
+
+_scratch = {}
+
+
+def _scratch_buf(kind, device, nbytes, floor=0):
+    """The uint8 scratch buffer of one ``kind`` of kernel on this device's current stream: kept between calls, replaced by
+    a larger one (never below ``floor`` bytes) when a call asks for more than it holds."""
+    key = (kind,) + _ws_key(device)
+    ws = _scratch.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(int(nbytes), floor), dtype=torch.uint8, device=device)
+        _scratch[key] = ws
+    return ws
+
+
+class _Exchange:
+    """The granule buffer of a kernel whose workgroups exchange data through tagged slots (the clustered BatchNorm, the
+    split LSTM recurrence) on one (device, stream): zeroed once, every launch given a range of tags no earlier launch
+    used.  The buffer's first word counts the bounded waits that ran out."""
+
+    TAG_LIMIT = 0xFFFFFFF0     # (32-bit tags: start over on a cleared buffer)
+
+    def __init__(self):
+        self.buf, self.tags, self.retired_errors = None, 0, 0
+
+    def _error_word(self):
+        return 0 if self.buf is None else int(self.buf[:4].view(torch.int32).item())
+
+    def reserve(self, device, nbytes, tags):
+        """(buffer of at least nbytes, tags handed out before this call): the launch owns tags [base, base + tags).
+        A buffer that is replaced by a larger one or cleared at the tag wrap hands its error word to the host-side
+        total first: one read-back (a host sync), only where a buffer is re-allocated or cleared - while the layers
+        of a first forward ask for their sizes (warm-up), never in the steady state."""
+        grow = self.buf is None or self.buf.numel() < nbytes
+        if grow or self.tags + tags + 1 >= self.TAG_LIMIT:
+            self.retired_errors += self._error_word()
+            if grow:
+                self.buf = torch.zeros(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+            else:
+                self.buf.zero_()
+            self.tags = 0
+        base = self.tags
+        self.tags += int(tags)
+        return self.buf, base
+
+    def errors(self):
+        """Bounded waits that ran out in every launch so far (cumulative over replaced buffers): one read-back."""
+        return self.retired_errors + self._error_word()
+
+
+_exchanges = {}
+
+
+def _exchange(kind, device):
+    return _exchanges.setdefault((kind,) + _ws_key(device), _Exchange())
+
+
+def _exchange_errors(kind, device):
+    ex = _exchanges.get((kind,) + _ws_key(device))
+    return 0 if ex is None else ex.errors()
 
 
 # --------------------------------------------------------------------------- GEMM / conv
@@ -284,12 +387,7 @@ def conv_bnlocal_tile_rows(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, 
     or None when the library does not take it in that form (the caller then runs the unfused sequence)."""
     d = _abi.ConvDesc(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x_img_stride, x_row_stride,
                       x_px_stride, w_row_stride, y_px_stride, ACT_NONE, 1.0)
-    r = lib().avs_conv2d_bnlocal_tile_rows(ctypes.byref(d), int(rows_per_group))
-    if r == _abi.E_UNSUPPORTED:
-        return None
-    if r < 0:
-        check(int(r), "avs_conv2d_bnlocal_tile_rows")
-    return int(r)
+    return _query(lib().avs_conv2d_bnlocal_tile_rows(ctypes.byref(d), int(rows_per_group)), "avs_conv2d_bnlocal_tile_rows")
 
 
 def conv_bncluster_ok(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x_img_stride, x_row_stride, x_px_stride,
@@ -299,12 +397,8 @@ def conv_bncluster_ok(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout,
     rows, groups of a multiple of 112 rows)?"""
     d = _abi.ConvDesc(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x_img_stride, x_row_stride,
                       x_px_stride, w_row_stride, y_px_stride, ACT_NONE, 1.0, 0, _abi.CLUSTER_PACKED if packed else 0)
-    r = lib().avs_conv2d_bncluster_workspace_bytes(ctypes.byref(d), int(rows_per_group), int(cluster))
-    if r == _abi.E_UNSUPPORTED:
-        return False
-    if r < 0:
-        check(int(r), "avs_conv2d_bncluster_workspace_bytes")
-    return True
+    return _query(lib().avs_conv2d_bncluster_workspace_bytes(ctypes.byref(d), int(rows_per_group), int(cluster)),
+                  "avs_conv2d_bncluster_workspace_bytes") is not None
 
 
 def conv_bnstats_ok(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x_img_stride, x_row_stride, x_px_stride,
@@ -314,59 +408,14 @@ def conv_bnstats_ok(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x
     outside the dense 1x1 / stride-1 shapes."""
     d = _abi.ConvDesc(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x_img_stride, x_row_stride, x_px_stride,
                       w_row_stride, y_px_stride, ACT_NONE, 1.0, 0, 0, _abi.X_F16P8 if x_p8 else 0)
-    r = lib().avs_conv2d_bnstats_workspace_bytes(ctypes.byref(d), int(rows_per_group))
-    if r == _abi.E_UNSUPPORTED:
-        return False
-    if r < 0:
-        check(int(r), "avs_conv2d_bnstats_workspace_bytes")
-    return True
-
-
-class _Exchange:
-    """The granule buffer of avs_conv2d_nhwc_bncluster on one (device, stream): zeroed once, epochs count up per call."""
-
-    def __init__(self):
-        self.buf, self.epoch = None, 0
-
-    def get(self, device, nbytes):
-        if self.buf is None or self.buf.numel() < nbytes:
-            self.buf = torch.zeros(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
-            self.epoch = 0
-        self.epoch += 1
-        if self.epoch >= 0xFFFFFFF0:      # (32-bit tags: start over on a cleared buffer)
-            self.buf.zero_()
-            self.epoch = 1
-        return self.buf, self.epoch
-
-
-_exchanges = {}
+    return _query(lib().avs_conv2d_bnstats_workspace_bytes(ctypes.byref(d), int(rows_per_group)),
+                  "avs_conv2d_bnstats_workspace_bytes") is not None
 
 
 def cluster_exchange_errors(device):
     """Waves whose bounded partner wait ran out in the clustered BatchNorm launches on this device's current stream so far
     (0 after healthy launches); reads the counter back (a host sync: for tests and debugging)."""
-    ex = _exchanges.get(_ws_key(device))
-    return 0 if ex is None or ex.buf is None else int(ex.buf[:4].view(torch.int32).item())
-
-
-_stats_ws = {}
-
-
-def _ws_key(device):
-    # one scratch buffer per (device, stream): launches on ONE stream are ordered, so consecutive layers can share
-    # it; two streams must not
-    return (device, torch.cuda.current_stream(device).cuda_stream)
-
-
-def _stats_workspace(device, nbytes):
-    """Scratch for the per-tile partial sums of avs_conv2d_nhwc_bnstats: one buffer per device and stream, grown on
-    demand."""
-    key = _ws_key(device)
-    ws = _stats_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
-        _stats_ws[key] = ws
-    return ws
+    return _exchange_errors("cluster", device)
 
 
 def conv2d_raw(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x, x_img_stride, x_row_stride, x_px_stride,
@@ -416,23 +465,20 @@ def conv2d_raw(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x, x_i
             if residual.dtype != y.dtype or residual.shape != (n * ho * wo, cout):
                 raise ValueError("residual must be [rows, cout] in the activation dtype")
         if cluster > 1:
-            need = lib().avs_conv2d_bncluster_workspace_bytes(ctypes.byref(d), int(rpg), int(cluster))
-            if need < 0:
-                check(int(need), "avs_conv2d_bncluster_workspace_bytes")
-            xbuf, epoch = _exchanges.setdefault(_ws_key(x.device), _Exchange()).get(x.device, need)
+            need = _query(lib().avs_conv2d_bncluster_workspace_bytes(ctypes.byref(d), int(rpg), int(cluster)),
+                          "avs_conv2d_bncluster_workspace_bytes", may_decline=False)
+            xbuf, base = _exchange("cluster", x.device).reserve(x.device, need, 1)    # one tag per launch: 1, 2, 3, ...
             _timed("conv", dtype, flops, lambda: check(
                 lib().avs_conv2d_nhwc_bncluster(ctypes.byref(d), _p(x, x_off), _p(wt), _p(y, y_off), int(rpg), int(cluster),
-                                                _p(gamma), _p(beta), float(eps), _p(residual),
-                                                residual.stride(0) if residual is not None else 0, _p(xbuf), xbuf.numel(),
-                                                int(epoch), _stream()),
+                                                _p(gamma), _p(beta), float(eps), _p(residual), _ld(residual), _p(xbuf),
+                                                xbuf.numel(), base + 1, _stream()),     # (the library refuses tag 0)
                 "avs_conv2d_nhwc_bncluster"),
                    cbytes + (float(es) * n * ho * wo * cout if residual is not None else 0.0),
                    form=f"{'packed ' if packed else ''}clustered tile-local BatchNorm {kh}x{kw}")
             return None
         _timed("conv", dtype, flops, lambda: check(
             lib().avs_conv2d_nhwc_bnlocal(ctypes.byref(d), _p(x, x_off), _p(wt), _p(y, y_off), int(rpg), _p(gamma),
-                                          _p(beta), float(eps), _p(residual),
-                                          residual.stride(0) if residual is not None else 0, _stream()),
+                                          _p(beta), float(eps), _p(residual), _ld(residual), _stream()),
             "avs_conv2d_nhwc_bnlocal"),
                cbytes + (float(es) * n * ho * wo * cout if residual is not None else 0.0), form=f"tile-local BatchNorm {kh}x{kw}")
         return None
@@ -446,38 +492,25 @@ def conv2d_raw(dtype, n, h, w, cin, kh, kw, sh, sw, ph, pw, ho, wo, cout, x, x_i
         raise ValueError("the fused-statistics convolution takes no bias / activation")
     rows = n * ho * wo
     groups = (rows + rpg - 1) // rpg
-    need = lib().avs_conv2d_bnstats_workspace_bytes(ctypes.byref(d), int(rpg))
     if x_affine is not None:
-        if need == _abi.E_UNSUPPORTED:
-            return None
-        xsc, xsf, xrelu = x_affine
-        _dev(xsc, xsf)
-        if xsc.dtype != torch.float32 or xsf.dtype != torch.float32 or not (xsc.is_contiguous() and xsf.is_contiguous()):
-            raise ValueError("x_affine scale / shift must be contiguous fp32 [groups, cin]")
-        if need < 0:
-            check(int(need), "avs_conv2d_bnstats_workspace_bytes")
-        ws = _stats_workspace(x.device, need)
-        scale = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
-        shift = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
+        xsc, xsf = _group_affine(x_affine[:2], "x_affine", "conv2d_raw", groups, cin)
+    # the library declines a shape: the caller runs another form - but no other form reads an AVS_F16P8 input (the input
+    # affine form is itself the alternative, so it only ever declines)
+    need = _query(lib().avs_conv2d_bnstats_workspace_bytes(ctypes.byref(d), int(rpg)), "avs_conv2d_bnstats_workspace_bytes",
+                  may_decline=x_affine is not None or not formats)
+    if need is None:
+        return None
+    ws = _scratch_buf("stats", x.device, need, 1 << 20)
+    scale = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
+    shift = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
+    if x_affine is not None:
         st = []
         _timed("conv", dtype, flops, lambda: st.append(
             lib().avs_conv2d_nhwc_bnstats_xin(ctypes.byref(d), _p(x, x_off), _p(wt), _p(y, y_off), int(rpg), _p(gamma),
                                               _p(beta), float(eps), _p(scale), _p(shift), _p(ws), ws.numel(), _p(xsc),
-                                              _p(xsf), int(bool(xrelu)), _stream())),
+                                              _p(xsf), int(bool(x_affine[2])), _stream())),
                cbytes, form=f"convolution + statistics {kh}x{kw}, input affine")
-        if st[0] == _abi.E_UNSUPPORTED:
-            return None
-        check(st[0], "avs_conv2d_nhwc_bnstats_xin")
-        return scale, shift
-    if need == _abi.E_UNSUPPORTED:
-        if formats:
-            check(int(need), "avs_conv2d_bnstats_workspace_bytes")   # no other form reads an AVS_F16P8 input
-        return None
-    if need < 0:
-        check(int(need), "avs_conv2d_bnstats_workspace_bytes")
-    ws = _stats_workspace(x.device, need)
-    scale = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
-    shift = torch.empty((groups, cout), dtype=torch.float32, device=x.device)
+        return None if _query(st[0], "avs_conv2d_nhwc_bnstats_xin") is None else (scale, shift)
     _timed("conv", dtype, flops, lambda: check(
         lib().avs_conv2d_nhwc_bnstats(ctypes.byref(d), _p(x, x_off), _p(wt), _p(y, y_off), int(rpg), _p(gamma),
                                       _p(beta), float(eps), _p(scale), _p(shift), _p(ws), ws.numel(), _stream()),
@@ -506,21 +539,17 @@ def conv1x1_bn(x2d, wt, rows_per_group, gamma, beta, eps, out2d, residual=None, 
     # algorithmic HBM bytes: read x once, write y once (+ read the residual); the second pass re-reads from L2
     nbytes = 2.0 * rows * (k + n * (2 if residual is not None else 1))
     if in_affine is not None:
-        isc, ish = in_affine
-        _dev(isc, ish)
-        if isc.shape != (groups, k) or ish.shape != (groups, k) or not isc.is_contiguous() or not ish.is_contiguous():
-            raise ValueError("in_affine must be contiguous fp32 [groups, K]")
+        isc, ish = _group_affine(in_affine, "in_affine", "conv1x1_bn", groups, k)
         _timed("convbn", AVS_BF16, nbytes, lambda: check(
             lib().avs_conv1x1_bn_in_bf16(_p(x2d), x2d.stride(0), k, _p(isc), _p(ish), _p(wt), wt.stride(0), n,
                                          rows_per_group, groups, _p(gamma), _p(beta), float(eps), _p(residual),
-                                         residual.stride(0) if residual is not None else 0, 1 if relu else 0,
-                                         _p(out2d), out2d.stride(0), _stream()), "avs_conv1x1_bn_in_bf16"))
+                                         _ld(residual), 1 if relu else 0, _p(out2d), out2d.stride(0), _stream()),
+            "avs_conv1x1_bn_in_bf16"))
         return out2d
     _timed("convbn", AVS_BF16, nbytes, lambda: check(
         lib().avs_conv1x1_bn_bf16(_p(x2d), x2d.stride(0), k, _p(wt), wt.stride(0), n, rows_per_group, groups,
-                                  _p(gamma), _p(beta), float(eps), _p(residual),
-                                  residual.stride(0) if residual is not None else 0, 1 if relu else 0, _p(out2d),
-                                  out2d.stride(0), _stream()), "avs_conv1x1_bn_bf16"))
+                                  _p(gamma), _p(beta), float(eps), _p(residual), _ld(residual), 1 if relu else 0,
+                                  _p(out2d), out2d.stride(0), _stream()), "avs_conv1x1_bn_bf16"))
     return out2d
 
 
@@ -529,38 +558,39 @@ def gram_supported(k, n):
     return k in (64, 128) and n % 32 == 0
 
 
-def bn_gram_affine(x2d, wt, rows_per_group, gamma, beta, eps, in_affine=None, store_input=False):
-    """Folded BatchNorm affine (scale, shift) fp32 [groups, N] of y = a . wt^T per group of rows, computed from the
-    Gram matrix of a WITHOUT forming y (avs_bn_gram_affine_bf16).  a = x2d, or bf16(relu(x2d * isc + ish)) with
-    in_affine = (isc, ish) fp32 [groups, K].  K in {64, 128}, N a multiple of 32.
-    store_input (with in_affine): x2d is overwritten IN PLACE with a."""
+def _bn_gram_affine(what, code, x2d, wt, rows_per_group, gamma, beta, eps, in_affine, store_input):
+    """bn_gram_affine (code AVS_BF16: bf16 tensors) and bn_gram_affine_h2 (AVS_F16X2: float32-typed tensors of f16x2 slots)."""
     _dev(x2d, wt, gamma, beta)
     _rowmajor2d(x2d, "x")
     _rowmajor2d(wt, "w")
     rows, k = x2d.shape
     n = wt.shape[0]
-    if x2d.dtype != torch.bfloat16 or wt.dtype != torch.bfloat16:
-        raise TypeError("bn_gram_affine is the bf16 throughput path")
+    stored, entry = ((torch.bfloat16, "avs_bn_gram_affine_bf16") if code == AVS_BF16 else
+                     (torch.float32, "avs_bn_gram_affine_f16x2"))
+    if x2d.dtype != stored or wt.dtype != stored:
+        raise TypeError(f"{what}: x and w must be {stored}, got {x2d.dtype} and {wt.dtype}")
     if rows % rows_per_group or wt.shape[1] != k:
-        raise ValueError("bn_gram_affine: shapes do not match")
+        raise ValueError(f"{what}: shapes do not match")
     groups = rows // rows_per_group
-    isc = ish = None
-    if in_affine is not None:
-        isc, ish = in_affine
-        _dev(isc, ish)
-        if isc.shape != (groups, k) or ish.shape != (groups, k) or not isc.is_contiguous() or not ish.is_contiguous():
-            raise ValueError("in_affine must be contiguous fp32 [groups, K]")
+    isc, ish = _group_affine(in_affine, "in_affine", what, groups, k) if in_affine is not None else (None, None)
+    if store_input and in_affine is None:
+        raise ValueError(f"{what}: store_input needs in_affine")
     scale = torch.empty((groups, n), dtype=torch.float32, device=x2d.device)
     shift = torch.empty((groups, n), dtype=torch.float32, device=x2d.device)
-    # algorithmic HBM bytes: x read once
-    if store_input and in_affine is None:
-        raise ValueError("store_input needs in_affine")
-    _timed("gram", AVS_BF16, 2.0 * rows * k * (2 if store_input else 1), lambda: check(
-        lib().avs_bn_gram_affine_bf16(_p(x2d), x2d.stride(0), k, _p(isc), _p(ish), _p(wt), wt.stride(0), n,
-                                      rows_per_group, groups, _p(gamma), _p(beta), float(eps), _p(scale), _p(shift),
-                                      _p(x2d) if store_input else None, x2d.stride(0), _stream()),
-        "avs_bn_gram_affine_bf16"))
+    # algorithmic HBM bytes: x read once (and written once with store_input)
+    _timed("gram", code, float(x2d.element_size()) * rows * k * (2 if store_input else 1), lambda: check(
+        getattr(lib(), entry)(_p(x2d), x2d.stride(0), k, _p(isc), _p(ish), _p(wt), wt.stride(0), n, rows_per_group, groups,
+                              _p(gamma), _p(beta), float(eps), _p(scale), _p(shift), _p(x2d) if store_input else None,
+                              x2d.stride(0), _stream()), entry))
     return scale, shift
+
+
+def bn_gram_affine(x2d, wt, rows_per_group, gamma, beta, eps, in_affine=None, store_input=False):
+    """Folded BatchNorm affine (scale, shift) fp32 [groups, N] of y = a . wt^T per group of rows, computed from the
+    Gram matrix of a WITHOUT forming y (avs_bn_gram_affine_bf16).  a = x2d, or bf16(relu(x2d * isc + ish)) with
+    in_affine = (isc, ish) fp32 [groups, K].  K in {64, 128}, N a multiple of 32.
+    store_input (with in_affine): x2d is overwritten IN PLACE with a."""
+    return _bn_gram_affine("bn_gram_affine", AVS_BF16, x2d, wt, rows_per_group, gamma, beta, eps, in_affine, store_input)
 
 
 def conv1x1_affine(x2d, wt, rows_per_group, scale, shift, out2d, residual=None, relu=True, in_affine=None,
@@ -569,7 +599,8 @@ def conv1x1_affine(x2d, wt, rows_per_group, scale, shift, out2d, residual=None, 
     scale / shift fp32 [groups, N] contiguous (a BatchNorm already folded, e.g. by bn_gram_affine); a = x2d or
     bf16(relu(x2d * isc + ish)) with in_affine = (isc, ish) fp32 [groups, K]; res_affine = (rsc, rsh) fp32
     [groups, N]: the residual is a raw convolution output, added as residual * rsc + rsh."""
-    _dev(x2d, wt, out2d, residual, scale, shift)
+    what = "conv1x1_affine"
+    _dev(x2d, wt, out2d, residual)
     _rowmajor2d(x2d, "x")
     _rowmajor2d(wt, "w")
     _rowmajor2d(out2d, "out")
@@ -580,31 +611,17 @@ def conv1x1_affine(x2d, wt, rows_per_group, scale, shift, out2d, residual=None, 
     if rows % rows_per_group or wt.shape[1] != k or out2d.shape != (rows, n):
         raise ValueError("conv1x1_affine: shapes do not match")
     groups = rows // rows_per_group
-    for a in (scale, shift):
-        if a.dtype != torch.float32 or a.shape != (groups, n) or not a.is_contiguous():
-            raise ValueError("scale / shift must be contiguous fp32 [groups, N]")
+    _group_affine((scale, shift), None, what, groups, n)
     if residual is not None:
         _rowmajor2d(residual, "residual")
-    isc, ish = in_affine if in_affine is not None else (None, None)
-    if in_affine is not None:
-        _dev(isc, ish)
-        if isc.shape != (groups, k) or ish.shape != (groups, k) or not isc.is_contiguous() or not ish.is_contiguous():
-            raise ValueError("in_affine must be contiguous fp32 [groups, K]")
-    rsc, rsh = res_affine if res_affine is not None else (None, None)
-    if res_affine is not None:
-        _dev(rsc, rsh)
-        if residual is None:
-            raise ValueError("res_affine without a residual")
-        for a in (rsc, rsh):
-            if a.dtype != torch.float32 or a.shape != (groups, n) or not a.is_contiguous():
-                raise ValueError("res_affine must be contiguous fp32 [groups, N]")
+    isc, ish = _group_affine(in_affine, "in_affine", what, groups, k) if in_affine is not None else (None, None)
+    rsc, rsh = _res_affine(res_affine, residual, what, groups, n)
     # algorithmic HBM bytes: read x, write y (+ read the residual)
     nbytes = 2.0 * rows * (k + n * (2 if residual is not None else 1))
     _timed("convbn", AVS_BF16, nbytes, lambda: check(
         lib().avs_conv1x1_affine_bf16(_p(x2d), x2d.stride(0), k, _p(isc), _p(ish), _p(wt), wt.stride(0), n,
-                                      rows_per_group, groups, _p(scale), _p(shift), _p(residual),
-                                      residual.stride(0) if residual is not None else 0, _p(rsc), _p(rsh),
-                                      1 if relu else 0, _p(out2d), out2d.stride(0), _stream()),
+                                      rows_per_group, groups, _p(scale), _p(shift), _p(residual), _ld(residual), _p(rsc),
+                                      _p(rsh), 1 if relu else 0, _p(out2d), out2d.stride(0), _stream()),
         "avs_conv1x1_affine_bf16"))
     return out2d
 
@@ -628,32 +645,7 @@ def bn_gram_affine_h2(x2d, wt, rows_per_group, gamma, beta, eps, in_affine=None,
     """AVS_F16X2 counterpart of bn_gram_affine (avs_bn_gram_affine_f16x2): x2d / wt are f16x2 tensors (float32-typed).
     Returns the folded affine (scale, shift) fp32 [groups, N] of the BatchNorm of y = a . wt^T.  in_affine = (isc, ish)
     fp32 [groups, K]: x2d is a raw convolution output, a = relu(x2d * isc + ish); store_input: a overwrites x2d."""
-    _dev(x2d, wt, gamma, beta)
-    _rowmajor2d(x2d, "x")
-    _rowmajor2d(wt, "w")
-    _f32(x2d, "x")
-    _f32(wt, "w")
-    rows, k = x2d.shape
-    n = wt.shape[0]
-    if rows % rows_per_group or wt.shape[1] != k:
-        raise ValueError("bn_gram_affine_h2: shapes do not match")
-    groups = rows // rows_per_group
-    isc = ish = None
-    if in_affine is not None:
-        isc, ish = in_affine
-        _dev(isc, ish)
-        if isc.shape != (groups, k) or ish.shape != (groups, k) or not isc.is_contiguous() or not ish.is_contiguous():
-            raise ValueError("in_affine must be contiguous fp32 [groups, K]")
-    if store_input and in_affine is None:
-        raise ValueError("store_input needs in_affine")
-    scale = torch.empty((groups, n), dtype=torch.float32, device=x2d.device)
-    shift = torch.empty((groups, n), dtype=torch.float32, device=x2d.device)
-    _timed("gram", AVS_F16X2, 4.0 * rows * k * (2 if store_input else 1), lambda: check(
-        lib().avs_bn_gram_affine_f16x2(_p(x2d), x2d.stride(0), k, _p(isc), _p(ish), _p(wt), wt.stride(0), n,
-                                       rows_per_group, groups, _p(gamma), _p(beta), float(eps), _p(scale), _p(shift),
-                                       _p(x2d) if store_input else None, x2d.stride(0), _stream()),
-        "avs_bn_gram_affine_f16x2"))
-    return scale, shift
+    return _bn_gram_affine("bn_gram_affine_h2", AVS_F16X2, x2d, wt, rows_per_group, gamma, beta, eps, in_affine, store_input)
 
 
 def conv2d_affine(dtype, n, h, w, cin, sh, sw, ho, wo, cout, x, x_img_stride, x_row_stride, x_px_stride, wt,
@@ -672,20 +664,18 @@ def conv2d_affine(dtype, n, h, w, cin, sh, sw, ho, wo, cout, x, x_img_stride, x_
         if residual.shape[-1] != cout or residual.data.shape[0] != n * ho * wo:
             raise ValueError("an AVS_F16P8 residual is dense [rows, cout]")
         residual, formats = residual.data, formats | _abi.RES_F16P8
-    _dev(x, wt, y, scale, shift, residual)
+    _dev(x, wt, y, residual)
     d = _abi.ConvDesc(dtype, n, h, w, cin, 1, 1, sh, sw, 0, 0, ho, wo, cout, x_img_stride, x_row_stride, x_px_stride,
                       w_row_stride, y_px_stride, ACT_RELU if relu else ACT_NONE, 1.0, int(w_layout), int(variant), formats)
     rows = n * ho * wo
     groups = (rows + rows_per_group - 1) // rows_per_group
-    for a in (scale, shift):
-        if a.dtype != torch.float32 or a.shape != (groups, cout) or not a.is_contiguous():
-            raise ValueError("scale / shift must be contiguous fp32 [groups, cout]")
-    rsc, rsh = res_affine if res_affine is not None else (None, None)
+    _group_affine((scale, shift), None, "conv2d_affine", groups, cout)
+    rsc, rsh = _res_affine(res_affine, residual, "conv2d_affine", groups, cout)
     if residual is not None and not res_p8:
         _rowmajor2d(residual, "residual")
         if residual.shape != (rows, cout):
             raise ValueError("residual must be [rows, cout]")
-    ldr = 0 if residual is None else (cout if res_p8 else residual.stride(0))
+    ldr = cout if res_p8 else _ld(residual)
     flops = 2.0 * rows * cout * cin
     nbytes = (4.0 * rows * cin + (3.0 if formats & _abi.Y_F16P8 else 4.0) * rows * cout
               + (0.0 if residual is None else (3.0 if res_p8 else 4.0) * rows * cout))
@@ -793,7 +783,16 @@ def pull_copy(host_pinned, dst, workgroups=16):
     return dst
 
 
-_stem_ws = {}
+def _stem_outputs(frames_u8, dtype, frames_per_group):
+    """The fused stems' shared part: the frame check, then (pooled map [n,56,56,64] of dtype, scale, shift [groups, 64])."""
+    if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape[1:]) != (224, 224, 3) or not frames_u8.is_contiguous():
+        raise ValueError("frames must be contiguous uint8 [n,224,224,3]")
+    n, dev = frames_u8.shape[0], frames_u8.device
+    groups = n // frames_per_group if frames_per_group else 0
+    y = torch.empty((n, 56, 56, 64), dtype=dtype, device=dev)
+    scale = torch.empty((groups, 64), dtype=torch.float32, device=dev)
+    shift = torch.empty((groups, 64), dtype=torch.float32, device=dev)
+    return y, scale, shift
 
 
 def stem_conv_bn_pool(frames_u8, wt, denom, mean, std, frames_per_group, gamma, beta, eps, relu=True, apply=True):
@@ -803,21 +802,11 @@ def stem_conv_bn_pool(frames_u8, wt, denom, mean, std, frames_per_group, gamma, 
     apply=False: y is the pooled RAW map and the consumers apply relu(scale * y + shift) while staging it (their
     in_affine operand) - the finishing pass over the map is saved."""
     _dev(frames_u8, wt, gamma, beta)
-    if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape[1:]) != (224, 224, 3) or not frames_u8.is_contiguous():
-        raise ValueError("frames must be contiguous uint8 [n,224,224,3]")
+    y, scale, shift = _stem_outputs(frames_u8, torch.bfloat16, frames_per_group)
     if wt.dtype != torch.bfloat16 or wt.shape[0] != 64 or wt.shape[1] != 224:
         raise ValueError("stem weight must be bf16 [64, 224] (7 kernel rows x 8 pixels x 4 channels)")
     n = frames_u8.shape[0]
-    dev = frames_u8.device
-    y = torch.empty((n, 56, 56, 64), dtype=torch.bfloat16, device=dev)
-    groups = n // frames_per_group if frames_per_group else 0
-    scale = torch.empty((groups, 64), dtype=torch.float32, device=dev)
-    shift = torch.empty((groups, 64), dtype=torch.float32, device=dev)
-    need = int(lib().avs_stem_workspace_bytes(n))
-    ws = _stem_ws.get(_ws_key(dev))
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        _stem_ws[_ws_key(dev)] = ws
+    ws = _scratch_buf("stem", frames_u8.device, int(lib().avs_stem_workspace_bytes(n)), 256)
     m3 = (c_float * 3)(*[float(v) for v in mean])
     s3 = (c_float * 3)(*[float(v) for v in std])
     # algorithmic: 2 * 147 MACs per output, uint8 frames in, pooled bf16 map out
@@ -855,21 +844,11 @@ def stem_conv_pool_h2(frames_u8, wimg, frames_per_group, gamma, beta, eps):
     activation is relu(scale * y + shift), applied by the consumer (bn_gram_affine_h2's in_affine).
     wimg = stem_h2_operands(...)."""
     _dev(frames_u8, wimg, gamma, beta)
-    if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape[1:]) != (224, 224, 3) or not frames_u8.is_contiguous():
-        raise ValueError("frames must be contiguous uint8 [n,224,224,3]")
+    y, scale, shift = _stem_outputs(frames_u8, torch.float32, frames_per_group)
     if wimg.dtype != torch.float32 or tuple(wimg.shape) != (64, 224):
         raise ValueError("the weight operand must come from stem_h2_operands: f16x2 [64, 224]")
     n = frames_u8.shape[0]
-    dev = frames_u8.device
-    y = torch.empty((n, 56, 56, 64), dtype=torch.float32, device=dev)
-    groups = n // frames_per_group if frames_per_group else 0
-    scale = torch.empty((groups, 64), dtype=torch.float32, device=dev)
-    shift = torch.empty((groups, 64), dtype=torch.float32, device=dev)
-    need = int(lib().avs_stem_f16x2_workspace_bytes(n))
-    ws = _stem_ws.get(_ws_key(dev))
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        _stem_ws[_ws_key(dev)] = ws
+    ws = _scratch_buf("stem", frames_u8.device, int(lib().avs_stem_f16x2_workspace_bytes(n)), 256)
     # algorithmic: 2 * 147 MACs per output, uint8 frames in, pooled f16x2 map out
     _timed("stem", AVS_F16X2, 2.0 * n * 112 * 112 * 64 * 147, lambda: check(
         lib().avs_stem_conv_pool_f16x2(_p(frames_u8), n, _p(wimg), wimg.stride(0), int(frames_per_group),
@@ -916,9 +895,8 @@ def bn_apply(x2d, scale, shift, group_rows=None, max_group_rows=0, residual=None
     nbytes = float(rows) * c * x2d.element_size() * (3 if residual is not None else 2)
     _timed("bn_apply", code, nbytes, lambda: check(
         lib().avs_bn_apply(code, _p(x2d), rows, c, x2d.stride(0), _p(group_rows), g,
-                           int(max_group_rows), _p(scale), _p(shift), _p(residual),
-                           residual.stride(0) if residual is not None else 0, act, _p(out), out.stride(0),
-                           _stream()), "avs_bn_apply"))
+                           int(max_group_rows), _p(scale), _p(shift), _p(residual), _ld(residual), act, _p(out),
+                           out.stride(0), _stream()), "avs_bn_apply"))
     return out
 
 
@@ -1057,9 +1035,6 @@ def stft_mel_max(wave, window, cos_t, sin_t, fb, fb_lo, fb_hi):
     return gmax
 
 
-_segmean_ws = {}
-
-
 def stft_mel_segmean(wave, window, cos_t, sin_t, fb, fb_lo, fb_hi, blocks, seg_block, seg_frames, gmax=None,
                      top_db=80.0, out_log2=None, out_db=None):
     """Time means per segment of log2(mel + 1e-6) (out_log2 [nseg, >= nmel]) and of the top_db-clamped dB mel (out_db)
@@ -1078,19 +1053,14 @@ def stft_mel_segmean(wave, window, cos_t, sin_t, fb, fb_lo, fb_hi, blocks, seg_b
         gmax = torch.empty(1, dtype=torch.float32, device=wave.device)
     need = int(lib().avs_stft_mel_segmean_workspace_bytes(nblocks, nmel, int(out_log2 is not None),
                                                           int(out_db is not None), find_max))
-    key = _ws_key(wave.device)
-    ws = _segmean_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=wave.device)
-        _segmean_ws[key] = ws
+    ws = _scratch_buf("segmean", wave.device, need, 1 << 16)
     t = wave.numel()
     nbytes = 4.0 * t + 4.0 * nseg * nmel * (int(out_log2 is not None) + int(out_db is not None))
     _timed("audio", AVS_F32, nbytes, lambda: check(
         lib().avs_stft_mel_segmean_f32(_p(wave), t, _p(window), _p(cos_t), _p(sin_t), _p(fb), _p(fb_lo), _p(fb_hi), nmel,
                                        _p(blocks), nblocks, _p(seg_block), _p(seg_frames), nseg, _p(gmax), find_max,
-                                       float(top_db), _p(out_log2), out_log2.stride(0) if out_log2 is not None else 0,
-                                       _p(out_db), out_db.stride(0) if out_db is not None else 0, _p(ws), ws.numel(),
-                                       _stream()),
+                                       float(top_db), _p(out_log2), _ld(out_log2), _p(out_db), _ld(out_db), _p(ws),
+                                       ws.numel(), _stream()),
         "avs_stft_mel_segmean_f32"))
     return out_log2, out_db
 
@@ -1107,18 +1077,13 @@ def stft_mel_segmean_batch(waves, track_off, track_len, window, cos_t, sin_t, fb
     nblocks, nseg = blocks.shape[0], seg_frames.numel()
     gmax = torch.empty(max(ntracks, 1), dtype=torch.float32, device=waves.device)
     need = int(lib().avs_stft_mel_segmean_workspace_bytes(nblocks, nmel, int(out_log2 is not None), int(out_db is not None), 1))
-    key = _ws_key(waves.device)
-    ws = _segmean_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=waves.device)
-        _segmean_ws[key] = ws
+    ws = _scratch_buf("segmean", waves.device, need, 1 << 16)
     nbytes = 4.0 * waves.numel() + 4.0 * nseg * nmel * (int(out_log2 is not None) + int(out_db is not None))
     _timed("audio", AVS_F32, nbytes, lambda: check(
         lib().avs_stft_mel_segmean_batch_f32(_p(waves), _p(track_off), _p(track_len), ntracks, _p(window), _p(cos_t), _p(sin_t),
                                              _p(fb), _p(fb_lo), _p(fb_hi), nmel, _p(blocks), nblocks, _p(seg_block),
-                                             _p(seg_frames), nseg, _p(gmax), float(top_db), _p(out_log2),
-                                             out_log2.stride(0) if out_log2 is not None else 0, _p(out_db),
-                                             out_db.stride(0) if out_db is not None else 0, _p(ws), ws.numel(), _stream()),
+                                             _p(seg_frames), nseg, _p(gmax), float(top_db), _p(out_log2), _ld(out_log2),
+                                             _p(out_db), _ld(out_db), _p(ws), ws.numel(), _stream()),
         "avs_stft_mel_segmean_batch_f32"))
     return out_log2, out_db, gmax
 
@@ -1136,23 +1101,15 @@ def stft_mel_shots(waves, track_off, track_len, shots, window, cos_t, sin_t, fb,
     ntracks, nshot, nblocks = track_len.numel(), seg_frames.numel(), blocks.shape[0]
     gmax = torch.empty(max(nshot, 1), dtype=torch.float32, device=waves.device)
     need = int(lib().avs_stft_mel_shots_workspace_bytes(nblocks, nmel, int(out_log2 is not None), int(out_db is not None)))
-    key = _ws_key(waves.device)
-    ws = _segmean_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=waves.device)
-        _segmean_ws[key] = ws
+    ws = _scratch_buf("segmean", waves.device, need, 1 << 16)
     nbytes = 4.0 * waves.numel() + 4.0 * nshot * nmel * (int(out_log2 is not None) + int(out_db is not None))
     _timed("audio", AVS_F32, nbytes, lambda: check(
         lib().avs_stft_mel_shots_f32(_p(waves), waves.numel(), _p(track_off), _p(track_len), ntracks, _p(shots), nshot,
                                      _p(window), _p(cos_t), _p(sin_t), _p(fb), _p(fb_lo), _p(fb_hi), nmel, _p(blocks), nblocks,
-                                     _p(seg_block), _p(seg_frames), _p(gmax), float(top_db), _p(out_log2),
-                                     out_log2.stride(0) if out_log2 is not None else 0, _p(out_db),
-                                     out_db.stride(0) if out_db is not None else 0, _p(ws), ws.numel(), _stream()),
+                                     _p(seg_block), _p(seg_frames), _p(gmax), float(top_db), _p(out_log2), _ld(out_log2),
+                                     _p(out_db), _ld(out_db), _p(ws), ws.numel(), _stream()),
         "avs_stft_mel_shots_f32"))
     return out_log2, out_db, gmax
-
-
-_vggish_ws = {}
 
 
 def vggish_examples(waves, ex_start, basis_t, fb, fb_lo, fb_hi):
@@ -1167,12 +1124,7 @@ def vggish_examples(waves, ex_start, basis_t, fb, fb_lo, fb_hi):
     out = torch.empty((nex, _abi.SHARED["AVS_VGG_FRAMES"], nmel), dtype=torch.float32, device=waves.device)
     if nex == 0:
         return out
-    need = int(lib().avs_vggish_examples_workspace_bytes(nex))
-    key = _ws_key(waves.device)
-    ws = _vggish_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=waves.device)
-        _vggish_ws[key] = ws
+    ws = _scratch_buf("vggish", waves.device, int(lib().avs_vggish_examples_workspace_bytes(nex)))
     check(lib().avs_vggish_examples_f32(_p(waves), waves.numel(), _p(ex_start), nex, _p(basis_t), basis_t.shape[1], _p(fb),
                                         _p(fb_lo), _p(fb_hi), nmel, _p(out), _p(ws), ws.numel(), _stream()),
           "avs_vggish_examples_f32")
@@ -1222,37 +1174,16 @@ LSTM_SPLIT_MAX_RECURRENCES = 208    # AUTO takes the four-CU form up to this man
 #                                     recurrence per CU is the better use of the chip
 
 
-class _LstmExchange:
-    """Granule workspace of the split recurrence on one (device, stream): zeroed once; `epoch` = tags handed out so far."""
-
-    def __init__(self):
-        self.buf, self.epoch = None, 0
-
-    def get(self, device, nbytes, steps):
-        if self.buf is None or self.buf.numel() < nbytes:
-            self.buf = torch.zeros(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
-            self.epoch = 0
-        if self.epoch + steps + 2 >= 0xFFFFFFF0:      # (32-bit tags: start over on a cleared buffer)
-            self.buf.zero_()
-            self.epoch = 0
-        e = self.epoch
-        self.epoch += int(steps) + 1
-        return self.buf, e
-
-
-_lstm_exchanges = {}
-
-
 def _lstm_split_ws(device, ndir, nseq, rows):
-    ex = _lstm_exchanges.setdefault(_ws_key(device), _LstmExchange())
-    return ex.get(device, lib().avs_lstm_split_workspace_bytes(ndir, nseq), rows)
+    """(granule workspace of the split recurrence, first tag of this launch): a launch over `rows` time steps owns
+    rows + 1 tags - 0, rows + 1, ..."""
+    return _exchange("lstm", device).reserve(device, lib().avs_lstm_split_workspace_bytes(ndir, nseq), rows + 1)
 
 
 def lstm_split_errors(device):
     """Workgroups whose bounded partner wait ran out in the split-recurrence launches on this device's current stream so far
     (0 after healthy launches); reads the counter back (a host sync)."""
-    ex = _lstm_exchanges.get(_ws_key(device))
-    return 0 if ex is None or ex.buf is None else int(ex.buf[:4].view(torch.int32).item())
+    return _exchange_errors("lstm", device)
 
 
 def _lstm_takes_split(variant, hidden, ndir, nseq):
