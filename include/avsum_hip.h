@@ -22,7 +22,7 @@
  *     (exact fmaf chain; the parity mode).  AVS_BF16 = bf16 operands, fp32
  *     accumulate on the bf16 MFMA (the throughput mode).  AVS_F32_ACC64
  *     (avs_gemm_nt / avs_conv2d_nhwc only) = fp32 operands and fp32 MFMA over
- *     each 16-element slice of the reduction, slices summed in fp64: used for
+ *     each reduction step (16 elements; 32 for long reductions), steps summed in fp64: used for
  *     the STFT, where a long fp32 running sum would lose the quiet bins.
  *     AVS_F32_SPLIT (avs_gemm_nt / avs_conv2d_nhwc[_bnstats] only) = fp32 operands
  *     in memory, products on the bf16 MFMA: every operand element is split into
@@ -402,7 +402,16 @@ int avs_conv1x1_affine_bf16(const void* d_x, int64_t lin_stride, int k, const fl
  * Replaces nn.Linear (models/av_model.py:10-15,29-31; models/attention.py:8-11;
  * features/extractors.py:193), the LSTM input projections (av_model.py:18-23),
  * the in/out projections of nn.MultiheadAttention (av_model.py:26) and the two
- * einsums of models/attention.py:21,23.  K, lda, ldb multiples of 16 bytes.  */
+ * einsums of models/attention.py:21,23.  K, lda, ldb, stride_a and stride_b
+ * multiples of 16 bytes, A and B 16-byte aligned; ldb >= K; lda >= 0, and
+ * lda = 0 is a broadcast row (every row of A is the one row).  C is free: any
+ * ldc >= N, any stride_c (batch entries may interleave in the columns as long as
+ * they do not overlap) and any element-aligned d_c are accepted, and nothing
+ * outside [M, N] of a batch entry is written; the bf16 store is vectorised
+ * (16 bytes) only for a 16-byte-aligned d_c with 16-byte row strides, and goes
+ * element by element otherwise.  M = 0 is AVS_OK and launches nothing.
+ * (tests/test_gpu_gemm_f64.py holds every kernel instance behind this entry
+ * point to float64 on these layouts.)                                        */
 int avs_gemm_nt(int dtype, int m, int n, int k,
                 const void* d_a, int64_t lda, int64_t stride_a,
                 const void* d_b, int64_t ldb, int64_t stride_b,
