@@ -229,7 +229,11 @@ extern "C" int avs_frames_normalize_u8(int dtype, const uint8_t* d_src, int n, i
 // ---------------------------------------------------------------------------
 // cv2.resize(..., INTER_LINEAR) for uint8, 3 channels: 11-bit fixed-point
 // coefficients, horizontal pass in int32, vertical pass with the >>4, >>16, +2, >>2
-// rounding of OpenCV's VResizeLinear.  [3P-memory: OpenCV source absent here]
+// rounding of OpenCV's VResizeLinear.  What pins it: every output byte lies within a derived bound (0.88 grey levels:
+// coefficient rounding, the >> 4 and >> 16 truncations, the final rounding) of the float64 bilinear resize with
+// half-pixel centres, and equals a 32-bit CPU restatement (tests/pixel_f64_inputs.py: resize_bound,
+// tests/test_gpu_pixel_f64.py).  What still rests on memory: bit parity with OpenCV itself [3P-memory: OpenCV source
+// absent here].
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void cv_linear_coef(int d, double scale, int smax, int& s0, int& s1, int& c0, int& c1) {
   float f = (float)((d + 0.5) * scale - 0.5);
@@ -944,13 +948,14 @@ extern "C" int avs_hsv_frame_diff_u8(const uint8_t* d_frames, int n, int h, int 
   AVS_REQUIRE(d_frames && d_sums, AVS_E_ARG, "avs_hsv_frame_diff_u8: null pointer");
   const int ph = (h + step - 1) / step, pw = (w + step - 1) / step;  // len(range(0, h, step))
   AVS_REQUIRE((long long)ph * pw * 255 < (1ll << 32), AVS_E_SHAPE, "avs_hsv_frame_diff_u8: frame too large for u32 sums");
+  // (every refusal before the memset: a refused call writes nothing)
+  AVS_REQUIRE(n - 1 <= 65535, AVS_E_SHAPE, "avs_hsv_frame_diff_u8: at most 65536 frames per call");
   hipError_t e = hipMemsetAsync(d_sums, 0, sizeof(uint32_t) * 3 * (size_t)n, (hipStream_t)stream);
   if (e != hipSuccess) {
     avs_set_error("avs_hsv_frame_diff_u8: memset failed: %s", hipGetErrorString(e));
     return AVS_E_HIP;
   }
   if (n == 1) return AVS_OK;
-  AVS_REQUIRE(n - 1 <= 65535, AVS_E_SHAPE, "avs_hsv_frame_diff_u8: at most 65536 frames per call");
   int bx = (int)avs_cdiv((long long)ph * pw, 256 * 8);
   if (bx < 1) bx = 1;
   if (bx > 64) bx = 64;

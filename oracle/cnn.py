@@ -30,7 +30,10 @@ STD = torch.tensor([0.229, 0.224, 0.225]).view(3, 1, 1)
 # ----------------------------------------------------------------------------- preprocessing
 def cv_resize_linear_u8(img, dh, dw):
     """OpenCV resize(INTER_LINEAR) for uint8 HWC [3P-memory]: coefficients rounded to 11 bits,
-    horizontal pass in int32, vertical pass ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2 >> 2."""
+    horizontal pass in int32, vertical pass ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2 >> 2.
+    Pinned by tests/test_pixel_f64_host.py: within the derived bound (0.88 grey levels, tests/pixel_f64_inputs.py
+    resize_bound) of the float64 bilinear resize with half-pixel centres, measured 0.80.  Bit parity with OpenCV itself
+    still rests on memory."""
     sh, sw = img.shape[:2]
     if (sh, sw) == (dh, dw):
         return img.copy()

@@ -3,7 +3,10 @@ PySceneDetect (features/extractors.py:388-393: ``detect(video_path, ContentDetec
 
 Third-party, absent from /root/reference and unpinned (scenedetect; OpenCV for the colour conversion):
 restated from the published algorithms [3P-memory] => PARITY UNPINNED; pinned by analytic known answers in
-tests/test_oracle_analytic.py (primary colours -> H 0/60/120, grey -> S = H = 0, cuts of a synthetic video).
+tests/test_oracle_analytic.py (primary colours -> H 0/60/120, grey -> S = H = 0, cuts of a synthetic video); the colour
+conversion also by tests/test_pixel_f64_host.py, on all 2^24 colours, within the bounds its 12-bit tables allow of the
+float64 definition of HSV (V exact, S within 0.5311, H within 0.6556 on the circle).  Bit parity with OpenCV itself still
+rests on memory.
 """
 import numpy as np
 

@@ -1,6 +1,7 @@
 """Analytic known-answer pins for the parts of the oracle whose reference arithmetic is third-party and
 absent (torchaudio, torchvision, cv2): PARITY UNPINNED against the libraries themselves, pinned here by
-closed-form facts."""
+closed-form facts.  The colour conversion and the uint8 resize are no longer pinned by known answers alone:
+test_pixel_f64_host.py holds both to derived bounds of their float64 definitions (all 2^24 colours; every resize case)."""
 import math
 
 import numpy as np
