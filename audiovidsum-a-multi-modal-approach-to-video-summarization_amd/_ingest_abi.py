@@ -1,0 +1,73 @@
+"""ctypes binding of libavsum_ingest.so, the NV12 entry points, DERIVED from include/avsum_ingest.h with the reader of
+_header.py exactly as _optim_abi.py derives libavsum_optim.so's: argument types, enumerators, shared sizes and the ABI
+version are what the header says - none is typed here.  The library shares nothing with the other two.
+
+No CPU fallback: a missing library, or a non-zero status, raises.
+"""
+import ctypes
+import functools
+import os
+
+# torch first, for the reason _abi.py gives: its HIP runtime must be the one this process initialises
+import torch  # noqa: F401
+
+from ._header import Header
+
+_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
+HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "avsum_ingest.h")
+LIB_PATH = os.path.join(_PKG_DIR, "lib", "libavsum_ingest.so")
+
+
+@functools.lru_cache(maxsize=None)
+def load_header():
+    """include/avsum_ingest.h, read and parsed once per process."""
+    with open(HEADER_PATH) as f:
+        return Header(f.read())
+
+
+_HEADER = load_header()
+SHARED = _HEADER.constants     # every enumerator and shared size of the header by its C name
+ABI_VERSION = SHARED["AVSI_ABI_VERSION"]
+SHIFT = SHARED["AVSI_SHIFT"]
+MAX_COEF = SHARED["AVSI_MAX_COEF"]
+MATRIX_INTS = SHARED["AVSI_MATRIX_INTS"]
+MAX_DIFF_FRAMES = SHARED["AVSI_MAX_DIFF_FRAMES"]
+_SIGNATURES = _HEADER.signatures()
+
+
+class AvsiError(RuntimeError):
+    pass
+
+
+_lib = None
+
+
+def declared_symbols():
+    """Names of every function include/avsum_ingest.h declares."""
+    return sorted(_HEADER.prototypes)
+
+
+def lib():
+    """Load libavsum_ingest.so once; raise loudly if it has not been built."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise AvsiError(f"{LIB_PATH} is missing: the HIP extension has not been built "
+                        "(run __graft_entry__.build() or `make -C <package>/csrc`). There is no CPU fallback.")
+    handle = ctypes.CDLL(LIB_PATH)
+    for name, (res, args) in _SIGNATURES.items():
+        fn = getattr(handle, name)
+        fn.restype = res
+        fn.argtypes = args
+    if handle.avsi_abi_version() != ABI_VERSION:
+        raise AvsiError(f"ABI version mismatch: libavsum_ingest.so reports {handle.avsi_abi_version()}, the header "
+                        f"says {ABI_VERSION}")
+    _lib = handle
+    return _lib
+
+
+def check(status, what):
+    if status != 0:
+        msg = lib().avsi_last_error()
+        raise AvsiError(f"{what} failed with status {status}: {msg.decode() if msg else ''}")

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..audio import MelPlan
+from ..ingest import Nv12Frames, nv12_resize_gather, nv12_to_bgr
 from ..cnn import InceptionV3Runner, Inception3, ResNet50Runner, RESNET_MEAN, RESNET_STD, resnet50_trunk
 from ..vggish import VGGish
 
@@ -106,26 +107,44 @@ class VisualFeatureExtractor(nn.Module):
             ops.segment_mean(inc, seg, out[:, 2048:])
         return out[0].cpu().numpy()
 
-    def embed_shots(self, frames_u8, plan):
+    @staticmethod
+    def _pass_inputs(frames, index, count, count_t, matrix):
+        """The trunks' inputs of one pass of embed_shots: {(224, 224): uint8 [count,224,224,3], (299, 299): ...} of the
+        frames ``index[:count]``, read where they lie - BGR rows or NV12 surfaces - and resized by one launch; a trunk
+        whose input size is the frame size gets the gathered (and, for NV12, converted) frames themselves."""
+        nv12 = isinstance(frames, Nv12Frames)
+        h, w = frames.shape[1:3]
+        sizes = [s for s in ((224, 224), (299, 299)) if s != (h, w)]
+        if nv12:
+            resized = dict(zip(sizes, nv12_resize_gather(frames, index, count, sizes, matrix)))
+        else:
+            resized = dict(zip(sizes, ops.resize_gather(frames, index, count, sizes)))
+        if len(sizes) < 2:
+            resized[(h, w)] = nv12_to_bgr(frames, index, count, matrix) if nv12 else ops.gather_rows(frames, index, count_t)
+        return resized
+
+    def embed_shots(self, frames_u8, plan, matrix="bt601"):
         """forward for every shot of a ragged batch of videos: fp32 [S, 4096] on the device, row s what forward returns
         for the sampled frames of shot s of ``plan`` (an ops.StageOneTables; zeros for an empty shot).  ``frames_u8``:
-        device uint8 [N,h,w,3], the videos concatenated.  Per pass of the plan - whole BatchNorm groups of one size, so
-        both trunks take their uniform forms - the pass's frames are gathered (and resized to 224x224 and 299x299 by one
+        device uint8 [N,h,w,3], the videos concatenated, or an ingest.Nv12Frames of them (converted by ``matrix`` as they
+        are read: the rows of embed_shots(nv12_to_bgr(frames), plan), bit for bit).  Per pass of the plan - whole BatchNorm
+        groups of one size, so both trunks take their uniform forms - the pass's frames are gathered (and resized to 224x224 and 299x299 by one
         launch) straight from ``frames_u8``, and the two trunks write the pass's rows of one [F, 4096] buffer; two
         segment_mean_perm launches then average every shot's rows, in the order of its frames.  The BatchNorm groups are
         the ones forward builds shot by shot; only the summation order of their statistics may differ."""
         ops._tables_arg(plan, ops.StageOneTables, "embed_shots")
-        ops._device_arg(frames_u8, "frames", "embed_shots", (torch.uint8,), shape=(plan.frames, None, None, 3),
-                        device=plan.device)
-        dev, (h, w) = frames_u8.device, frames_u8.shape[1:3]
-        sizes = [s for s in ((224, 224), (299, 299)) if s != (h, w)]
+        if isinstance(frames_u8, Nv12Frames):
+            ops._device_arg(frames_u8.data, "frames.data", "embed_shots", (torch.uint8,), shape=(plan.frames, None, None),
+                            device=plan.device)
+        else:
+            ops._device_arg(frames_u8, "frames", "embed_shots", (torch.uint8,), shape=(plan.frames, None, None, 3),
+                            device=plan.device)
+        dev = plan.device
         with torch.no_grad():
             feats = torch.empty((plan.nsamples, 4096), dtype=torch.float32, device=dev)
             for i, (gsz, lo, hi) in enumerate(plan.passes):
-                index = plan.pass_frame_index_t[lo:hi]
-                resized = dict(zip(sizes, ops.resize_gather(frames_u8, index, hi - lo, sizes)))
-                if len(sizes) < 2:
-                    resized[(h, w)] = ops.gather_rows(frames_u8, index, plan.pass_counts_t[i:i + 1])
+                resized = self._pass_inputs(frames_u8, plan.pass_frame_index_t[lo:hi], hi - lo,
+                                            plan.pass_counts_t[i:i + 1], matrix)
                 groups = torch.arange(0, hi - lo + 1, gsz, dtype=torch.int64)
                 self._resnet_runner.forward(resized[(224, 224)], groups, out=feats[lo:hi, :2048])
                 self._inception_runner.forward(resized[(299, 299)], out=feats[lo:hi, 2048:])
@@ -314,11 +333,13 @@ class AVProcessor:
             return np.array(visual), self.audio_extractor.forward_shots(waveform, bounds)
         return np.array(visual), np.array(audio)
 
-    def process_decoded_batch(self, frames_u8, video_offsets, waveforms, fps, shots=None, chunk_frames=4096):
+    def process_decoded_batch(self, frames_u8, video_offsets, waveforms, fps, shots=None, chunk_frames=4096,
+                              matrix="bt601"):
         """process_decoded(..., batch_audio=True) for a ragged batch of V videos: a list of V (visual, audio) pairs, pair v
         what process_decoded(frames of video v, waveforms[v], fps of video v, shots of video v, batch_audio=True) returns,
         in shapes and dtypes too (np.array([]) twice for a video without shots, a zero visual row for an empty shot).
-        ``frames_u8``: uint8 [N,h,w,3], the videos concatenated - a device tensor, or a numpy array uploaded once;
+        ``frames_u8``: uint8 [N,h,w,3], the videos concatenated - a device tensor, or a numpy array uploaded once - or an
+        ingest.Nv12Frames on the device (the decoder's surfaces, converted by ``matrix`` where they are read);
         ``video_offsets``: the host frame offsets [V + 1]; ``fps``: one number or one per video; ``shots``: one host
         [(start, end)] list per video, a features.shots.ShotBatchResult, or None to run detect_shots_batch.  The visual
         rows of all shots come from ONE VisualFeatureExtractor.embed_shots call (passes of at most ``chunk_frames``
@@ -326,22 +347,26 @@ class AVProcessor:
         from .shots import ShotBatchResult, detect_shots_batch
         if isinstance(frames_u8, np.ndarray):
             frames_u8 = torch.from_numpy(np.ascontiguousarray(frames_u8)).to(_device())
-        if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
-            raise ValueError("process_decoded_batch: frames must be a numpy array or a device tensor")
-        frames_u8 = frames_u8.contiguous()
+        nv12 = isinstance(frames_u8, Nv12Frames)
+        data = frames_u8.data if nv12 else frames_u8
+        if not torch.is_tensor(data) or not data.is_cuda:
+            raise ValueError("process_decoded_batch: frames must be a numpy array, a device tensor or Nv12Frames on the "
+                             "device")
+        if not nv12:
+            frames_u8 = frames_u8.contiguous()
         if shots is None:
-            shots = detect_shots_batch(frames_u8, video_offsets)
+            shots = detect_shots_batch(frames_u8, video_offsets, matrix=matrix)
         if isinstance(shots, ShotBatchResult):
             plan = ops.StageOneTables.from_result(shots, chunk_frames)
             if not np.array_equal(plan.offsets, np.asarray(video_offsets, dtype=np.int64).reshape(-1)):
                 raise ValueError("process_decoded_batch: the shots were detected for other video offsets")
         else:
-            plan = ops.StageOneTables(video_offsets, shots, chunk_frames, frames_u8.device)
+            plan = ops.StageOneTables(video_offsets, shots, chunk_frames, data.device)
         nv = plan.nvideos
         fps = [fps] * nv if np.isscalar(fps) else list(fps)
         if len(fps) != nv or len(waveforms) != nv:
             raise ValueError(f"process_decoded_batch: {nv} videos, {len(waveforms)} waveforms, {len(fps)} fps values")
-        visual = self.visual_extractor.embed_shots(frames_u8, plan).cpu().numpy()
+        visual = self.visual_extractor.embed_shots(frames_u8, plan, matrix).cpu().numpy()
         off = plan.shot_offsets
         bounds = [[(int(start / f * self.sr), int(end / f * self.sr)) for start, end in plan.shots[off[v]:off[v + 1]].tolist()]
                   for v, f in enumerate(fps)]

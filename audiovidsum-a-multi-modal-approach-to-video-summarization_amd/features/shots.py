@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..ingest import Nv12Frames, nv12_hsv_frame_diff_batch
 from ..ragged import exclusive_offsets
 
 DEFAULT_MIN_WIDTH = 256  # scenedetect.scene_manager.DEFAULT_MIN_WIDTH
@@ -141,23 +142,31 @@ class ShotBatchResult:
         return [[(int(start / f * sr), int(end / f * sr)) for start, end in shots] for f, shots in zip(fps, self.host())]
 
 
-def detect_shots_batch(frames_u8, video_offsets, threshold=27.0, min_scene_len=15, step=None):
+def detect_shots_batch(frames_u8, video_offsets, threshold=27.0, min_scene_len=15, step=None, matrix="bt601"):
     """detect_shots for a ragged batch: frames uint8 [N,h,w,3] on the device, the videos concatenated, and the host frame
     offsets [V + 1] (or a prepared ops.ShotTables) -> ShotBatchResult.  Four kernels' worth of launches - the frame
     differences of all videos, one workgroup per video for the cuts, a scan, one workgroup per video for the tables -
     and no host round trip: the cut lists, the shot table, the sampled-frame table and the BatchNorm micro-batch table
-    stay on the device until ShotBatchResult.host()."""
-    if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda:
+    stay on the device until ShotBatchResult.host().  ``frames_u8`` may be an ingest.Nv12Frames: the frame differences
+    then read the decoder's surfaces (converted by ``matrix`` on the way in, no BGR copy) and give the integers of the
+    converted frames; everything after them is the same launches."""
+    nv12 = isinstance(frames_u8, Nv12Frames)
+    data = frames_u8.data if nv12 else frames_u8
+    if not torch.is_tensor(data) or not data.is_cuda:
         raise ValueError("detect_shots_batch: frames must be a device tensor (there is no CPU fallback)")
     plan = video_offsets if isinstance(video_offsets, ops.ShotTables) else \
-        ops.ShotTables(video_offsets, min_scene_len, frames_u8.device)
+        ops.ShotTables(video_offsets, min_scene_len, data.device)
     if plan.min_scene_len != int(min_scene_len):
         raise ValueError(f"detect_shots_batch: the tables were built for min_scene_len {plan.min_scene_len}")
-    frames_u8 = frames_u8.contiguous()
+    if not nv12:
+        frames_u8 = frames_u8.contiguous()
     h, w = frames_u8.shape[1:3]
     step = downscale_factor(w) if step is None else int(step)
     pixels = float(len(range(0, h, step)) * len(range(0, w, step)))
-    sums = ops.hsv_frame_diff_batch(frames_u8, plan, step, raw=True)
+    if nv12:
+        sums = nv12_hsv_frame_diff_batch(frames_u8, plan, step, raw=True, matrix=matrix)
+    else:
+        sums = ops.hsv_frame_diff_batch(frames_u8, plan, step, raw=True)
     cuts, totals = ops.shot_cuts_batch(plan, sums, pixels, threshold)
     return ShotBatchResult(plan, sums, cuts, totals, ops.shot_tables(plan, cuts, totals))
 
