@@ -24,13 +24,21 @@ backward made of C-ABI calls: the probabilities are RECOMPUTED per batch element
 dP = dctx.V^T, dS = alpha P (dP - rowsum(P dP)) (avs_softmax_bwd_rows_f32), dQ = dS.K, dK = dS^T.Q, dV = P^T.dctx as
 NT GEMMs on transposed copies (avs_transpose_f32), the projection gradients as in the scorer's backward
 (ops.grad_weight / grad_input / colsum).  The backward materialises [H, T, T] (it is a training path: T is a clip).
+
+The ragged form, ``forward_rows(x_rows, offsets)``: the videos' rows concatenated, [R, E] -> [R, E], every video attended
+on its own (the layout of train_rows and of every other ragged stage).  Its core is libavsum_attn.so (attn.py): the
+exact-fp32 fused forward with the log-sum-exp saved, and under autograd ``_MHSARowsFunction``, a backward of three fused
+launches (delta, dK/dV, dQ) that rebuilds the probabilities tile by tile: nothing of size [T, T] is allocated in either
+direction, the saved tensors are x, q, k, v, ctx [R, E] and lse [R, H], there is no loop over the videos, and every
+gradient is the same bits from run to run and from batch to batch.  ``fused_backward = True`` sends ``forward`` under
+autograd through the same path (uniform offsets) where the head dim is 64, 128 or 256.
 """
 import math
 
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import attn, ops
 from .._abi import BIAS_NONE, BIAS_ROW
 
 
@@ -49,14 +57,61 @@ class MultiHeadSelfAttention(nn.Module):
         # (400 MB at T = 5000).  Measured on MI355X, E = 1024, H = 4, whole forward, T = 300 / 1800 / 5000: split fused
         # 0.375 / 0.63 / 1.40 ms, fp32 fused 0.49 / 1.11 / 2.69 ms, batched GEMMs 0.376 / 0.60 / 2.30 ms.
         self.use_flash = "auto"
+        # False: under autograd ``forward`` goes through _MHSAFunction, whose backward materialises [H, T, T].  True: where
+        # the head dim is 64, 128 or 256 it runs as forward_rows on x.reshape(B * T, E) with uniform offsets - the exact
+        # fp32 fused forward and the fused backward, O(B * T * E) memory (other head dims keep _MHSAFunction).
+        self.fused_backward = False
+        self._uniform_tables = {}     # (B, T, device) -> ops.AttnTable of the dense batch, uploaded once
+
+    def _wants_grad(self, x):
+        return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
 
     def forward(self, x):
         if not x.is_cuda:
             raise RuntimeError("MultiHeadSelfAttention runs on the MI355X HIP path only: move inputs with .cuda()")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if self.fused_backward and self.dim_head in attn.HEAD_DIMS and x.dim() == 3 and x.shape[1] > 0 \
+                and self._wants_grad(x):
+            b, t, e = x.shape
+            key = (b, t, x.device)
+            if key not in self._uniform_tables:
+                self._uniform_tables[key] = ops.AttnTable.uniform(b, t, device=x.device)
+            return self.forward_rows(x.reshape(b * t, e), self._uniform_tables[key]).view(b, t, e)
+        if self._wants_grad(x):
             return _MHSAFunction.apply(self, x, self.query.weight, self.query.bias, self.key.weight, self.key.bias,
                                        self.value.weight, self.value.bias, self.out.weight, self.out.bias)
         return self._forward(x)[0]
+
+    def forward_rows(self, x_rows, offsets):
+        """x_rows [R, E] on the device, the rows of V videos one after another; ``offsets`` the host row offsets [V + 1]
+        (0 first, R last) or an ops.AttnTable built from them (built once, reused from step to step) -> [R, E]: every
+        video attended over its own rows only, the same bits alone and in any batch.  Exact fp32 throughout; head dims
+        other than 64, 128 and 256 raise a ValueError (the batched-GEMM path is dense-only).  With gradients enabled
+        the backward is fused (module docstring)."""
+        if not x_rows.is_cuda:
+            raise RuntimeError("MultiHeadSelfAttention runs on the MI355X HIP path only: move inputs with .cuda()")
+        if x_rows.dim() != 2 or x_rows.shape[1] != self.num_heads * self.dim_head:
+            raise ValueError(f"forward_rows: x_rows must be [R, {self.num_heads * self.dim_head}], got "
+                             f"{list(x_rows.shape)}")
+        if self.dim_head not in attn.HEAD_DIMS:
+            raise ValueError(f"forward_rows: head dim {self.dim_head} must be one of {attn.HEAD_DIMS}")
+        table = offsets if isinstance(offsets, ops.AttnTable) else ops.AttnTable(offsets, device=x_rows.device)
+        if table.first_row != 0 or table.rows != x_rows.shape[0]:
+            raise ValueError(f"forward_rows: the offsets cover rows {table.first_row} .. {table.rows}, x_rows has "
+                             f"{x_rows.shape[0]} rows")
+        if self._wants_grad(x_rows):
+            return _MHSARowsFunction.apply(self, table, x_rows, self.query.weight, self.query.bias, self.key.weight,
+                                           self.key.bias, self.value.weight, self.value.bias, self.out.weight,
+                                           self.out.bias)
+        return self._forward_rows(x_rows, table)[0].to(x_rows.dtype)
+
+    def _forward_rows(self, x_rows, table):
+        """-> (out [R, E] fp32, (x2, q, k, v, ctx, lse))."""
+        x2 = x_rows.float().contiguous()
+        q = ops.linear(x2, self.query.weight, self.query.bias)
+        k = ops.linear(x2, self.key.weight, self.key.bias)
+        v = ops.linear(x2, self.value.weight, self.value.bias)
+        ctx, lse = attn.mhsa_rows_fwd(q, k, v, table, self.num_heads)
+        return ops.linear(ctx, self.out.weight, self.out.bias), (x2, q, k, v, ctx, lse)
 
     def _forward(self, x, keep=False):
         """-> (out [B,T,E], (x2, q, k, ctx) when ``keep``)."""
@@ -161,3 +216,35 @@ class _MHSAFunction(torch.autograd.Function):
             dx = (ops.grad_input(dq, wq) + ops.grad_input(dk, wk) + ops.grad_input(dv, wv)).view(b, t, e).to(xdtype)
         return (None, dx, ops.grad_weight(dq, x2), ops.colsum(dq), ops.grad_weight(dk, x2), ops.colsum(dk),
                 ops.grad_weight(dv, x2), ops.colsum(dv), g_wo, g_bo)
+
+
+class _MHSARowsFunction(torch.autograd.Function):
+    """forward = MultiHeadSelfAttention._forward_rows; backward = attn.mhsa_rows_bwd (delta, dK/dV, dQ: three launches for
+    the whole ragged batch) and the projection gradients of the scorer's backward, one call each.  Saved: x, q, k, v,
+    ctx [R, E] and lse [R, H] - nothing with T * T entries."""
+
+    @staticmethod
+    def forward(ctx, mod, table, x, wq, bq, wk, bk, wv, bv, wo, bo):
+        out, (x2, q, k, v, att, lse) = mod._forward_rows(x.detach(), table)
+        ctx.table, ctx.heads, ctx.xdtype = table, mod.num_heads, x.dtype
+        ctx.save_for_backward(x2, q, k, v, att, lse, wq, wk, wv, wo)
+        return out.to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, q, k, v, att, lse, wq, wk, wv, wo = ctx.saved_tensors
+        need = ctx.needs_input_grad          # (mod, table, x, wq, bq, wk, bk, wv, bv, wo, bo)
+        dout2 = dout.float().contiguous()
+        g_wo = ops.grad_weight(dout2, att) if need[9] else None
+        g_bo = ops.colsum(dout2) if need[10] else None
+        if not any(need[2:9]):
+            return (None, None, None, None, None, None, None, None, None, g_wo, g_bo)
+        datt = ops.grad_input(dout2, wo)                              # [R, E], heads side by side
+        dq, dk, dv = attn.mhsa_rows_bwd(datt, q, k, v, att, lse, ctx.table, ctx.heads)
+        dx = None
+        if need[2]:
+            dx = (ops.grad_input(dq, wq) + ops.grad_input(dk, wk) + ops.grad_input(dv, wv)).to(ctx.xdtype)
+        return (None, None, dx,
+                ops.grad_weight(dq, x2) if need[3] else None, ops.colsum(dq) if need[4] else None,
+                ops.grad_weight(dk, x2) if need[5] else None, ops.colsum(dk) if need[6] else None,
+                ops.grad_weight(dv, x2) if need[7] else None, ops.colsum(dv) if need[8] else None, g_wo, g_bo)

@@ -11,7 +11,7 @@ import torch
 from . import _abi
 from ._abi import (ACT_NONE, ACT_RELU, AVS_BF16, AVS_F16X2, AVS_F32, AVS_F32_SPLIT, BIAS_COL, BIAS_NONE, BIAS_ROW, check,
                    lib)
-from .ragged import (EVAL_CHUNK, EVAL_COLS, EVAL_MAX_T, EVAL_TILE, FUSION_MAX_N, FUSION_MID_L, FUSION_SMALL_L,  # noqa: F401
+from .ragged import (ATTN_BWD_TILE, ATTN_FWD_TILE, AttnTable, EVAL_CHUNK, EVAL_COLS, EVAL_MAX_T, EVAL_TILE, FUSION_MAX_N, FUSION_MID_L, FUSION_SMALL_L,  # noqa: F401
                      KTS_MAX_SAMPLES, SHOT_INTERVAL, SHOT_MAX_FRAMES, SHOT_MICRO_BATCH, SUMMARY_MAX_CAPACITY, SUMMARY_MAX_ROWS,
                      EvalTables, FusionTables, KtsTables, RaggedOffsets, SeqTable, ShotTables, StageOneTables,
                      SummaryTables)
@@ -22,6 +22,7 @@ __all__ = [
     "clamp_topdb", "stft_mel_max", "stft_mel_segmean", "stft_mel_segmean_batch", "stft_mel_shots", "vggish_examples", "fill", "quantize", "resample", "lstm", "mha_batchaxis", "score_head", "mhsa_flash", "softmax_rows", "cdist", "dtw_path",
     "gather_scale", "FusionTables", "fusion_batch", "EvalTables", "eval_counts", "segment_mean_mask", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
     "SeqTable", "seq_shift_rows", "seq_mse",
+    "AttnTable",
     "ShotTables", "hsv_frame_diff_batch", "shot_cuts_batch", "shot_tables", "gather_rows",
     "SummaryTables", "shot_value_sums", "knapsack_batch", "mask_overlap_counts",
     "StageOneTables", "resize_gather", "segment_mean_perm",

@@ -1,11 +1,12 @@
 """Host plans of the ragged-batch layers: row offsets validated on the host and uploaded once (RaggedOffsets and the
-six tables built on it - EvalTables, SeqTable, ShotTables, StageOneTables, SummaryTables, KtsTables) and the pair tables of the
-batched fusion (FusionTables).
+seven tables built on it - EvalTables, SeqTable, AttnTable, ShotTables, StageOneTables, SummaryTables, KtsTables) and the
+pair tables of the batched fusion (FusionTables).
 Pure host code on numpy and torch: nothing here touches the kernel library, so the plans can be built and checked with
 ``device="cpu"`` where there is no GPU.  ops.py re-exports every name and holds the launch wrappers that take them."""
 import numpy as np
 import torch
 
+from ._attn_abi import load_header as _load_attn_header   # (the header's reader only: the library is not loaded here)
 from ._header import load as _load_header
 from .features.kts import KTS_MAX_SAMPLES, kts_penalties   # (pure numpy: the limit and the penalty of the definitions)
 
@@ -36,6 +37,13 @@ SUMMARY_MAX_ROWS = 1024       # score rows of one knapsack batch (grid y).  The 
 KTS_TILE = _H["AVS_KTS_TILE"]                # 64: rows and columns of a Gram tile
 KTS_MAX_VIDEOS = _H["AVS_KTS_MAX_VIDEOS"]    # 65535: videos of one batch (a grid dimension)
 _KTS_VIDEO_COLS = _H["AVS_KTS_VIDEO_COLS"]   # 10: int64 per row of the video table
+
+# include/avsum_attn.h: the tile sizes of the ragged-batch attention kernels
+_HA = _load_attn_header().constants
+ATTN_FWD_TILE = _HA["AVSA_FWD_TILE"]         # 128: queries of a forward workgroup
+ATTN_BWD_TILE = _HA["AVSA_BWD_TILE"]         # 32: keys of a dK/dV workgroup = queries of a dQ workgroup
+_ATTN_TILE_COLS = _HA["AVSA_TILE_COLS"]      # 2: int32 per row of a tile table
+_ATTN_MAX_ROWS = _HA["AVSA_MAX_ROWS"]        # 2^31 - 1: the last offset at most
 
 
 def exclusive_offsets(lengths):
@@ -143,6 +151,37 @@ class SeqTable(RaggedOffsets):
     def __init__(self, offsets_host, rows=None, device=None):
         super().__init__(offsets_host, "SeqTable", device=device, rows=rows)
         self.nseq, self.rows, self.max_t = self.count, self.total, self.max_len
+
+
+class AttnTable(RaggedOffsets):
+    """The host plan of one batch layout for the ragged-batch attention (attn.mhsa_rows_fwd / mhsa_rows_bwd,
+    MultiHeadSelfAttention.forward_rows), built once from the host row offsets [V + 1] of the sequences in the
+    concatenated projections (sequence v is rows offsets[v] .. offsets[v + 1]).
+
+    Host side (numpy): ``offsets``, ``lengths`` (int64), ``nseq``, ``first_row`` (= offsets[0]: the first sequence may
+    start after row 0), ``rows`` (= offsets[-1]: the buffers need at least that many rows), ``max_t``; ``fwd_tiles``
+    int32 [n_fwd, 2] = (sequence, tile of 128 queries) for the forward and ``bwd_tiles`` int32 [n_bwd, 2] = (sequence,
+    tile of 32) for the two gradient kernels, whose query tiles and key tiles are the same table - every sequence's
+    tiles 0 .. ceil(T_v / tile) - 1, sequence after sequence.  Device side: ``offsets_t`` int64 [V + 1], ``fwd_tiles_t``,
+    ``bwd_tiles_t``, uploaded once.  ``device="cpu"`` keeps everything on the host (the builder can be checked without
+    a GPU or the library).  Refused, each with a ValueError: an empty batch, an empty sequence (the offsets must
+    increase strictly), negative or decreasing offsets, 2^31 rows or more.  uniform(b, t) is the table of a dense
+    [b, t] batch."""
+
+    def __init__(self, offsets_host, device=None):
+        super().__init__(offsets_host, "AttnTable", device=device, zero_start=False, max_total=_ATTN_MAX_ROWS,
+                         total_inclusive=True)
+        self.nseq, self.first_row, self.rows, self.max_t = self.count, int(self.offsets[0]), self.total, self.max_len
+        self.fwd_tiles, self.bwd_tiles = (
+            np.stack(segment_tiles(-(-self.lengths // tile)), 1).astype(np.int32).reshape(-1, _ATTN_TILE_COLS)
+            for tile in (ATTN_FWD_TILE, ATTN_BWD_TILE))
+        self.n_fwd, self.n_bwd = self.fwd_tiles.shape[0], self.bwd_tiles.shape[0]
+        self.fwd_tiles_t, self.bwd_tiles_t = _upload(self.device, self.fwd_tiles, self.bwd_tiles)
+
+    @classmethod
+    def uniform(cls, b, t, device=None):
+        """The table of ``b`` sequences of ``t`` rows each, from row 0."""
+        return cls(np.arange(int(b) + 1, dtype=np.int64) * int(t), device=device)
 
 
 class ShotTables(RaggedOffsets):
