@@ -13,7 +13,7 @@ import re
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "avsum_hip.h")
 
 SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
-           "size_t": ctypes.c_size_t, "unsigned": ctypes.c_uint, "uint32_t": ctypes.c_uint}
+           "size_t": ctypes.c_size_t, "unsigned": ctypes.c_uint, "uint32_t": ctypes.c_uint, "uint64_t": ctypes.c_uint64}
 # what a pointer may point to (every pointer is passed as an address: c_void_p)
 _POINTEES = set(SCALARS) | {"void", "char", "int32_t", "uint8_t", "uint16_t", "uint64_t"}
 

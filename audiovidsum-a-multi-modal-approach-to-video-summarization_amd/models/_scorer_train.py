@@ -1,15 +1,16 @@
 """Training-mode forward + backward of AVBiLSTMModel on the MI355X (scripts/train_av_model.py:86-96).
 
 A torch.autograd.Function whose forward and backward are sequences of libavsum_hip.so calls: torch only owns
-the tensors, the RNG that draws the Dropout masks, and (in the caller's script) AdamW.  The rows are those of V >= 1
-videos, concatenated, with the device table of their row offsets: every video is its own B = 1 call of the reference
+the tensors, the RNG that draws the Dropout masks (unless the model is seeded: then the masks are counter-based,
+dropout.py, computed inside libavsum_dropout.so's kernels and never stored), and (in the caller's script) AdamW.
+The rows are those of V >= 1 videos, concatenated, with the device table of their row offsets: every video is its own B = 1 call of the reference
 model (the reference trains with B = 1, train_av_model.py:64,86-88) - its own four recurrences, and with B = 1 the
 attention is out_proj(v_proj(x)) and the query/key projections receive exactly zero gradient.  Everything
 else is row-wise.  AVBiLSTMModel.forward (V = 1, seq = [0, T]) and AVBiLSTMModel.train_rows both come through here.
 """
 import torch
 
-from .. import ops
+from .. import dropout, ops
 
 DROPOUT_P = 0.3  # models/av_model.py:11,14
 
@@ -18,7 +19,9 @@ class ScorerTrainFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, visual, audio, keep_v, keep_a, seq, *params):
         """visual [R, Dv], audio [R, Da], keep_* [R, hidden]; seq int64 [V + 1] on the device: the row offsets of the
-        videos (starts at 0, increases, ends at R - the caller has validated it on the host)."""
+        videos (starts at 0, increases, ends at R - the caller has validated it on the host).  keep_v a dropout.Draw
+        (keep_a is then ignored): the masks are the counter-based ones it names, branch 0 visual and branch 1 audio -
+        applied by dropout.apply, computed again by dropout.relu_bwd in the backward, held by nobody."""
         names = [n for n, _ in model.named_parameters()]
         pm = dict(zip(names, params))
         dev = visual.device
@@ -33,10 +36,15 @@ class ScorerTrainFunction(torch.autograd.Function):
         xproj = torch.empty((t, 16 * hid), dtype=torch.float32, device=dev)   # [v fwd | v rev | a fwd | a rev] x 4H
         whh_all = []
         col = 0
+        draw = keep_v if isinstance(keep_v, dropout.Draw) else None
         for tag, x, keep, fc, lstm in (("v", visual, keep_v, "visual_fc.0.", "visual_bilstm."),
                                        ("a", audio, keep_a, "audio_fc.0.", "audio_bilstm.")):
             r = ops.linear(x, pm[fc + "weight"], pm[fc + "bias"], ops.ACT_RELU)     # Linear + ReLU
-            emb = ops.mul(r, keep)                                                   # Dropout (inverted scaling)
+            if draw is None:
+                emb = ops.mul(r, keep)                                               # Dropout (inverted scaling)
+            else:
+                keep = None                                                          # nothing to hold for the backward
+                emb = dropout.apply(r, draw.seed, draw.p, draw.samples, int(tag == "a"), seq)
             wih = torch.cat([pm[lstm + "weight_ih_l0"], pm[lstm + "weight_ih_l0_reverse"]], 0)
             bih = torch.cat([pm[lstm + "bias_ih_l0"] + pm[lstm + "bias_hh_l0"],
                              pm[lstm + "bias_ih_l0_reverse"] + pm[lstm + "bias_hh_l0_reverse"]])
@@ -56,7 +64,7 @@ class ScorerTrainFunction(torch.autograd.Function):
         hid64 = ops.linear(attn, pm["scorer.0.weight"], pm["scorer.0.bias"], ops.ACT_RELU)
         scores = ops.score_head(hid64, pm["scorer.2.weight"].reshape(-1).contiguous(), pm["scorer.2.bias"])
 
-        ctx.names, ctx.saved, ctx.seq, ctx.e = names, saved, seq, e
+        ctx.names, ctx.saved, ctx.seq, ctx.e, ctx.draw = names, saved, seq, e, draw
         ctx.tail = (fused, val, attn, hid64, scores, w_v, w_o)
         ctx.pm = pm
         ctx.need_inputs = (ctx.needs_input_grad[1], ctx.needs_input_grad[2])
@@ -106,7 +114,10 @@ class ScorerTrainFunction(torch.autograd.Function):
             g[lstm + "weight_hh_l0"] = ops.grad_weight(da[:, :4 * hid], hprev_f)
             g[lstm + "weight_hh_l0_reverse"] = ops.grad_weight(da[:, 4 * hid:], hprev_r)
             demb = ops.grad_input(da, wih)
-            dr = ops.relu_dropout_bwd(demb, r, keep)
+            if ctx.draw is None:
+                dr = ops.relu_dropout_bwd(demb, r, keep)
+            else:
+                dr = dropout.relu_bwd(demb, r, ctx.draw.seed, ctx.draw.p, ctx.draw.samples, int(tag == "a"), ctx.seq)
             g[fc + "weight"] = ops.grad_weight(dr, x)
             g[fc + "bias"] = ops.colsum(dr)
             dinputs[tag] = dr

@@ -37,6 +37,45 @@ class AVBiLSTMModel(nn.Module):
         self.scorer = nn.Sequential(nn.Linear(hidden_dim * 2, 64), nn.ReLU(), nn.Linear(64, 1), nn.Sigmoid())
         self._prepared = None
         self._prepared_key = None
+        self._counter_dropout = None
+
+    # ------------------------------------------------------------------ Dropout masks
+    def seed_dropout(self, seed):
+        """``seed`` (an integer in [0, 2^64)): from now on the training-mode Dropout masks are counter-based
+        (dropout.py): a pure function of (seed, sample id of the video, branch, row inside the video, column), computed
+        inside the kernels that apply them and never stored - the same for a video alone and in any batch.  Every video
+        of a training call takes the next sample id of ``self.counter_dropout`` (a dropout.CounterDropout, whose
+        state() belongs beside a checkpoint: it is no part of state_dict()).  ``None`` (the state of a new model):
+        back to torch's generator.  An injected ``_dropout_keep`` wins over either; eval mode uses neither."""
+        from ..dropout import CounterDropout
+        self._counter_dropout = None if seed is None else CounterDropout(seed, self.visual_fc[2].p)
+        return self
+
+    @property
+    def counter_dropout(self):
+        """The dropout.CounterDropout of seed_dropout(seed), None without a seed."""
+        return getattr(self, "_counter_dropout", None)
+
+    def _training_masks(self, nseq, rows, device, samples=None):
+        """(keep_v, keep_a) of one training-mode pass over ``nseq`` videos of ``rows`` rows in all: the injected
+        tensors, else a dropout.Draw (twice) that names the counter-based masks, else two draws from torch's RNG."""
+        from ._scorer_train import dropout_keep
+        hidden = self.visual_fc[0].out_features
+        masks = getattr(self, "_dropout_keep", None)  # tests inject fixed masks here
+        if masks is not None:
+            return masks
+        counter = self.counter_dropout
+        if counter is None:
+            if samples is not None:
+                raise ValueError("sample ids need counter-based Dropout: call seed_dropout(seed) first")
+            return dropout_keep((rows, hidden), device), dropout_keep((rows, hidden), device)
+        from ..dropout import Draw, sample_table
+        if samples is None:
+            samples = counter.take(nseq)                      # consecutive ids: passed by value, nothing uploaded
+        elif not isinstance(samples, int):
+            samples = sample_table(samples, nseq, device)     # the caller's ids: validated, uploaded once
+        draw = Draw(counter.seed, counter.p, samples)
+        return draw, draw
 
     # ------------------------------------------------------------------ weights in kernel layout
     def _prepare(self):
@@ -109,7 +148,7 @@ class AVBiLSTMModel(nn.Module):
         return ops.score_head(hid64, s2.weight.reshape(-1), s2.bias)
 
     # ------------------------------------------------------------------ training on a ragged batch of videos
-    def train_rows(self, visual_rows, audio_rows, offsets):
+    def train_rows(self, visual_rows, audio_rows, offsets, samples=None):
         """Scores, with autograd attached, for the rows of V videos in one pass: the training-mode counterpart of
         score_rows and the V-video form of what forward() does for B = 1.
 
@@ -124,7 +163,12 @@ class AVBiLSTMModel(nn.Module):
         one for the audio branch, so for V > 1 torch's RNG is consumed differently from V per-video calls (which draw
         visual, audio, visual, audio, ...): the same distribution, other masks.  Tests inject
         ``model._dropout_keep = (keep_v, keep_a)``, [R, hidden] each.  Eval mode with gradients enabled: keep masks of
-        ones, as forward() does."""
+        ones, as forward() does.
+
+        After seed_dropout(seed) the masks are counter-based instead and torch's RNG is not touched: video v takes the
+        sample id ``counter_dropout.take(V) + v``, or ``samples[v]`` where the caller gives HOST ids [V] (integers in
+        [0, 2^63), validated and uploaded once; an int: the first of V consecutive ids).  A video's masks then depend on
+        (seed, its id) only: the V-video pass equals the V one-video calls bit for bit, Dropout included."""
         if not visual_rows.is_cuda or not audio_rows.is_cuda:
             raise RuntimeError("AVBiLSTMModel runs on the MI355X HIP path only: move inputs with .cuda()")
         if visual_rows.dim() != 2 or audio_rows.dim() != 2 or visual_rows.shape[0] != audio_rows.shape[0]:
@@ -132,22 +176,23 @@ class AVBiLSTMModel(nn.Module):
                              f"{tuple(audio_rows.shape)}")
         rows = visual_rows.shape[0]
         table = ops._seq_table(offsets, rows, visual_rows.device, "train_rows")
-        from ._scorer_train import ScorerTrainFunction, dropout_keep
+        from ._scorer_train import ScorerTrainFunction
         v = visual_rows.float().contiguous()
         a = audio_rows.float().contiguous()
         hidden = self.visual_fc[0].out_features
         if self.training:
-            masks = getattr(self, "_dropout_keep", None)  # tests inject fixed masks here
-            keep_v, keep_a = masks if masks is not None else (dropout_keep((rows, hidden), v.device),
-                                                              dropout_keep((rows, hidden), v.device))
-            if tuple(keep_v.shape) != (rows, hidden) or tuple(keep_a.shape) != (rows, hidden):
+            keep_v, keep_a = self._training_masks(table.nseq, rows, v.device, samples)
+            if isinstance(keep_v, torch.Tensor) and (tuple(keep_v.shape) != (rows, hidden)
+                                                     or tuple(keep_a.shape) != (rows, hidden)):
                 raise ValueError(f"the Dropout masks must be [{rows}, {hidden}]")
         else:
             keep_v = keep_a = torch.ones((rows, hidden), dtype=torch.float32, device=v.device)
         return ScorerTrainFunction.apply(self, v, a, keep_v, keep_a, table.offsets_t,
                                          *[p for _, p in self.named_parameters()])
 
-    def forward(self, visual, audio):
+    def forward(self, visual, audio, sample=None):
+        """``sample``: after seed_dropout(seed), the sample id this video's training-mode Dropout masks take (an
+        integer in [0, 2^63)); None takes the next id of ``counter_dropout``."""
         if not visual.is_cuda or not audio.is_cuda:
             raise RuntimeError("AVBiLSTMModel runs on the MI355X HIP path only: move inputs with .cuda()")
         if visual.dim() != 3 or audio.dim() != 3 or visual.shape[:2] != audio.shape[:2]:
@@ -165,12 +210,10 @@ class AVBiLSTMModel(nn.Module):
                                           "reference's training loop does")
             if t == 0:
                 raise ValueError("empty sequence")
-            from ._scorer_train import ScorerTrainFunction, dropout_keep
+            from ._scorer_train import ScorerTrainFunction
             hidden = self.visual_fc[0].out_features
             if self.training:
-                masks = getattr(self, "_dropout_keep", None)  # tests inject fixed masks here
-                keep_v, keep_a = masks if masks is not None else (dropout_keep((t, hidden), v.device),
-                                                                  dropout_keep((t, hidden), v.device))
+                keep_v, keep_a = self._training_masks(1, t, v.device, sample)
             else:
                 keep_v = keep_a = torch.ones((t, hidden), dtype=torch.float32, device=v.device)
             seq = torch.tensor([0, t], dtype=torch.int64, device=v.device)

@@ -15,6 +15,10 @@ of the per-video losses).  The default k = 1 is the reference's loop, untouched.
 ``train_on_dataset(..., optimizer="fused")`` replaces torch.optim.AdamW by optim.FusedAdamW (libavsum_optim.so: the whole
 step in at most three launches, optionally with global-norm clipping and the skip of a non-finite step, both decided on
 the device).  The default "torch" is the reference's optimiser, untouched.
+
+``train_on_dataset(..., dropout_seed=s)`` seeds the model's Dropout (AVBiLSTMModel.seed_dropout: counter-based masks,
+dropout.py) and gives the video at position i of the b-th drawn batch of 8 the sample id 8 * b + i, so its masks depend
+on (s, b, i) only - not on videos_per_step, not on the number of ranks.  The default None draws with torch, untouched.
 """
 import torch
 import torch.nn.functional as F
@@ -26,14 +30,15 @@ from ..ragged import exclusive_offsets
 from ..utils.alignments import align_shots_to_annotations
 
 
-def train_step(model, optimizer, features, frame_scores, device="cuda"):
-    """Lines 72-96 of the reference for one (features, frame_scores) item.  Returns the loss value."""
+def train_step(model, optimizer, features, frame_scores, device="cuda", sample=None):
+    """Lines 72-96 of the reference for one (features, frame_scores) item.  Returns the loss value.  ``sample``: the
+    sample id of this video's Dropout masks, for a model after seed_dropout(seed) (None: the model's next id)."""
     num_shots = features["visual"].shape[0]
     shot_scores = align_shots_to_annotations(shot_boundaries=[(0, num_shots)], annotations=frame_scores.numpy(),
                                              fps=30)
     visual = features["visual"].unsqueeze(0).to(device)
     audio = features["audio"].unsqueeze(0).to(device)
-    preds = model(visual, audio)
+    preds = model(visual, audio) if sample is None else model(visual, audio, sample=sample)
     loss = F.mse_loss(preds, shot_scores.to(device).float())
     optimizer.zero_grad()
     loss.backward()
@@ -69,14 +74,19 @@ def collate_videos(items):
     return torch.cat(vis), torch.cat(aud), torch.from_numpy(exclusive_offsets(lengths)), torch.cat(targets)
 
 
-def train_step_batch(model, optimizer, items, device="cuda"):
+def train_step_batch(model, optimizer, items, device="cuda", samples=None):
     """One optimiser step on V videos at once: one upload of the collated rows, one forward / backward over the ragged
     batch, the loss = the mean of the per-video MSEs - its gradient is the average of the per-video gradients, i.e.
     what V ranks that take one video each hold after dist.allreduce_gradients (the same step up to summation order).
-    Returns the per-video losses (a list of floats) from ONE download, after the step."""
+    Returns the per-video losses (a list of floats) from ONE download, after the step.  ``samples``: host sample ids
+    [V] of the videos' Dropout masks, for a model after seed_dropout(seed) (None: the model's next V ids); with them the
+    step IS the one V data-parallel ranks take with one video and its id each, Dropout included."""
     visual, audio, offsets, targets = collate_videos(items)
     table = ops.SeqTable(offsets, visual.shape[0], device)
-    preds = model.train_rows(visual.to(device), audio.to(device), table)
+    if samples is None:
+        preds = model.train_rows(visual.to(device), audio.to(device), table)
+    else:
+        preds = model.train_rows(visual.to(device), audio.to(device), table, samples=samples)
     losses = ops.seq_mse(preds, targets.to(device), table)
     loss = losses.mean()
     optimizer.zero_grad()
@@ -86,19 +96,24 @@ def train_step_batch(model, optimizer, items, device="cuda"):
     return losses.detach().cpu().tolist()
 
 
-def select_items(items, rank, world, videos_per_step):
-    """The videos of one drawn batch that this rank trains on: positions (rank + j * world) % len(items) for
+def select_positions(n, rank, world, videos_per_step):
+    """The positions in a drawn batch of ``n`` videos that this rank trains on: (rank + j * world) % n for
     j < videos_per_step, duplicates dropped (a short last batch yields fewer)."""
     picked = []
     for j in range(videos_per_step):
-        i = (rank + j * world) % len(items)
+        i = (rank + j * world) % n
         if i not in picked:
             picked.append(i)
-    return [items[i] for i in picked]
+    return picked
+
+
+def select_items(items, rank, world, videos_per_step):
+    """The videos of one drawn batch that this rank trains on: those at select_positions(len(items), ...)."""
+    return [items[i] for i in select_positions(len(items), rank, world, videos_per_step)]
 
 
 def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, device="cuda", videos_per_step=1,
-                     optimizer="torch", max_grad_norm=None, skip_nonfinite=False):
+                     optimizer="torch", max_grad_norm=None, skip_nonfinite=False, dropout_seed=None):
     """One process: the reference's loop exactly (its DataLoader, its global-RNG shuffle, item 0 of every batch of 8).
     With torch.distributed initialised (one process per GPU) it is data-parallel over that loop: rank 0's weights are
     broadcast first (C1), every rank draws the SAME shuffled batches of 8 (the shuffle seed comes from rank 0) and
@@ -114,7 +129,13 @@ def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, dev
     left unset.  optimizer = "fused": optim.FusedAdamW(lr=lr, max_grad_norm=..., skip_nonfinite=...), the same update
     in fused HIP kernels; the model's ``fused_optimizer`` attribute then holds it (stats(), state_dict()).  In a
     data-parallel run allreduce_gradients runs BEFORE step() (train_step, train_step_batch), so every rank sees the same
-    gradients, computes the same norm and takes the same skip decision: the replicas stay identical."""
+    gradients, computes the same norm and takes the same skip decision: the replicas stay identical.
+
+    dropout_seed = an integer in [0, 2^64): model.seed_dropout(dropout_seed), and every step hands the sample ids of its
+    videos to train_step(sample=...) / train_step_batch(samples=...): 8 * (index of the drawn batch, counted through
+    the epochs) + the video's position in that batch of 8.  A video's Dropout masks are then a function of (seed, batch
+    index, position) alone: the same under any videos_per_step and any number of ranks, and a run is replayed from the
+    seed.  torch's RNG is not consumed by Dropout.  None (the default): torch's generator draws the masks, as before."""
     import torch.distributed as tdist
     if optimizer not in ("torch", "fused"):
         raise ValueError(f"optimizer must be 'torch' or 'fused', got {optimizer!r}")
@@ -123,6 +144,8 @@ def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, dev
     if not isinstance(videos_per_step, int) or not 1 <= videos_per_step <= 8:
         raise ValueError(f"videos_per_step must be 1..8 (the loader draws batches of 8), got {videos_per_step!r}")
     model = (model or AVBiLSTMModel()).to(device)
+    if dropout_seed is not None:
+        model.seed_dropout(dropout_seed)
     rank, world, gen = 0, 1, None
     if tdist.is_initialized() and tdist.get_world_size() > 1:
         rank, world = tdist.get_rank(), tdist.get_world_size()
@@ -130,10 +153,13 @@ def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, dev
         seed = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int64).to(device)
         tdist.broadcast(seed, 0)
         gen = torch.Generator().manual_seed(int(seed.item()))
+    # a drawn batch -> (the positions of this rank's videos in it, the videos)
     if videos_per_step == 1:
-        collate = lambda items: items[rank % len(items)]  # noqa: E731
+        collate = lambda items: (rank % len(items), items[rank % len(items)])  # noqa: E731
     else:
-        collate = lambda items: select_items(items, rank, world, videos_per_step)  # noqa: E731
+        def collate(items):
+            positions = select_positions(len(items), rank, world, videos_per_step)
+            return positions, [items[i] for i in positions]
     loader = DataLoader(dataset, batch_size=8, shuffle=True, generator=gen, collate_fn=collate)
     if optimizer == "fused":
         from ..optim import FusedAdamW
@@ -141,16 +167,21 @@ def train_on_dataset(dataset, epochs=100, lr=1e-4, model=None, on_step=None, dev
         model.fused_optimizer = optimizer
     else:
         optimizer = torch.optim.AdamW(model.parameters(), lr=lr)
+    drawn = 0                                                # batches of 8 drawn so far, through the epochs
     for _ in range(epochs):
         model.train()
         if videos_per_step == 1:
-            for features, frame_scores in loader:
-                loss = train_step(model, optimizer, features, frame_scores, device)
+            for position, (features, frame_scores) in loader:
+                ids = {} if dropout_seed is None else {"sample": 8 * drawn + position}
+                loss = train_step(model, optimizer, features, frame_scores, device, **ids)
+                drawn += 1
                 if on_step is not None:
                     on_step(loss)
         else:
-            for items in loader:
-                losses = train_step_batch(model, optimizer, items, device)
+            for positions, items in loader:
+                ids = {} if dropout_seed is None else {"samples": [8 * drawn + i for i in positions]}
+                losses = train_step_batch(model, optimizer, items, device, **ids)
+                drawn += 1
                 if on_step is not None:
                     on_step(sum(losses) / len(losses))
         # the recurrences run split over four CUs (ops.lstm*): no bounded wait may have run out during the epoch
