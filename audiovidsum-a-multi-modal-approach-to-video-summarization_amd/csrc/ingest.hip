@@ -1,16 +1,18 @@
 // libavsum_ingest.so: NV12 frames read where they lie (include/avsum_ingest.h).  This file is the whole library.  It
-// includes avs_internal.h for its inline __device__ helpers only (bgr2hsv_u8, the one definition of the HSV pixel
-// arithmetic) and references no symbol of libavsum_hip.so: the error text, the argument checks and the launch check
-// below are its own.
+// includes avs_internal.h and pixel_bodies.h for their inline helpers only (bgr2hsv_u8, the one definition of the HSV
+// pixel arithmetic; the one text of the bilinear resize and of the shot scan) and references no symbol of
+// libavsum_hip.so: the error text, the argument checks and the launch check below are its own.
 //
 // Three kernels, one pixel definition (avsi_yuv2bgr, 32-bit integers throughout):
 //   nv12_to_bgr_kernel          four pixels - two chroma pairs - per thread, 12 output bytes
 //   nv12_resize_gather2_kernel  resize_gather2_kernel (stage1_batch.hip) with the band's luma and chroma rows staged into
-//                               LDS instead of its BGR rows, converted per tap: the same 11-bit bilinear arithmetic
-//   nv12_hsv_diff_batch_kernel  hsv_frame_diff_batch_kernel (shots_batch.hip) with the two pixels converted on the way in
+//                               LDS instead of its BGR rows, converted per tap: pixel_bodies.h's 11-bit bilinear arithmetic
+//   nv12_hsv_diff_batch_kernel  hsv_frame_diff_batch_kernel (shots_batch.hip) with the two pixels converted on the way
+//                               in: pixel_bodies.h's scan with an NV12 pixel source
 // Integers and fixed orders: two calls give the same bytes.
 #include <stdarg.h>
 #include "avs_internal.h"
+#include "pixel_bodies.h"
 #include "../../include/avsum_ingest.h"
 
 #define NI_THREADS 256
@@ -166,33 +168,10 @@ extern "C" int avsi_nv12_to_bgr_u8(const uint8_t* d_src, int64_t n, int h, int w
 }
 
 // ---------------------------------------------------------------------------
-// 2. cv2.resize(..., INTER_LINEAR) of gathered, converted frames.  ni_src_pos and ni_linear_coef are rg_src_pos and
-// rg_linear_coef of stage1_batch.hip, value for value (that file belongs to the other library; this one shares no
-// symbol with it), and the blend below is resize_gather2_kernel's.
+// 2. cv2.resize(..., INTER_LINEAR) of gathered, converted frames.  The coefficients, the band's source rows, the column
+// table and the blend are pixel_bodies.h's, the one text resize_gather2_kernel (stage1_batch.hip) runs too (that file
+// belongs to the other library: the two share inline text, no symbol).
 // ---------------------------------------------------------------------------
-__host__ __device__ __forceinline__ int ni_src_pos(int d, double scale, int smax, float& f) {
-  f = (float)((d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (s < 0) {
-    f = 0.f;
-    s = 0;
-  }
-  if (s >= smax - 1) {
-    f = 0.f;
-    s = smax - 1;
-  }
-  return s;
-}
-
-__device__ __forceinline__ void ni_linear_coef(int d, double scale, int smax, int& s0, int& s1, int& c0, int& c1) {
-  float f;
-  s0 = ni_src_pos(d, scale, smax, f);
-  s1 = min(s0 + 1, smax - 1);
-  c0 = __float2int_rn((1.f - f) * 2048.f);
-  c1 = __float2int_rn(f * 2048.f);
-}
-
 struct ni_dest {
   uint8_t* dst;        // [count, dh, dw, 3]
   int dh, dw, band;    // band: output rows per workgroup
@@ -206,21 +185,6 @@ struct ni_args {
 
 // LDS bytes of one staged row of w bytes: the row sits at its global address modulo 16
 __host__ __device__ __forceinline__ int ni_row_bytes(int w) { return ((w + 15) & ~15) + 16; }
-
-// bytes [0, n) of `l` to `g`, where l and g are congruent modulo 16: the bytes up to g's first 16-byte boundary and
-// after its last one singly, everything between as 16-byte units
-__device__ __forceinline__ void ni_stage_out(uint8_t* g, const uint8_t* l, int n) {
-  const int head = min(n, (int)((16u - (unsigned)(uintptr_t)g) & 15u));
-  const int nvec = (n - head) >> 4;
-  uint4* gv = reinterpret_cast<uint4*>(g + head);
-  const uint4* lv = reinterpret_cast<const uint4*>(l + head);
-  for (int j = threadIdx.x; j < nvec; j += NI_THREADS) gv[j] = lv[j];
-  const int tail0 = head + (nvec << 4);
-  for (int k = threadIdx.x; k < head + n - tail0; k += NI_THREADS) {
-    const int o = k < head ? k : tail0 + (k - head);
-    g[o] = l[o];
-  }
-}
 
 // grid (row of the index, band of output rows, destination).  A workgroup: (a) the column coefficients of its
 // destination into LDS; (b) the luma rows y_lo .. y_hi and the chroma rows y_lo >> 1 .. y_hi >> 1 its band reads, w
@@ -244,14 +208,9 @@ __global__ __launch_bounds__(NI_THREADS) void nv12_resize_gather2_kernel(avsi_fr
   uint8_t* chroma = luma + D.luma_rows * lrow;
   uint8_t* out_base = luma + D.rows * lrow;
 
-  for (int dx = threadIdx.x; dx < dw; dx += NI_THREADS) {
-    int x0, x1, a0, a1;
-    ni_linear_coef(dx, D.scale_x, sw, x0, x1, a0, a1);
-    coef[dx] = make_uint2((unsigned)x0 | ((unsigned)x1 << 16), (unsigned)a0 | ((unsigned)a1 << 16));
-  }
-  float fy;
-  const int y_lo = ni_src_pos(dy_lo, D.scale_y, sh, fy);
-  const int y_hi = min(ni_src_pos(dy_hi - 1, D.scale_y, sh, fy) + 1, sh - 1);
+  cv_coef_fill<NI_THREADS>(coef, dw, D.scale_x, sw);
+  int y_lo, y_hi;
+  cv_band_rows(dy_lo, dy_hi, D.scale_y, sh, y_lo, y_hi);
   const int c_lo = y_lo >> 1, c_hi = y_hi >> 1;
   const int nl = y_hi - y_lo + 1, nc = c_hi - c_lo + 1;
   const uint8_t* f_luma = F.src + r * F.frame_stride;
@@ -298,7 +257,7 @@ __global__ __launch_bounds__(NI_THREADS) void nv12_resize_gather2_kernel(avsi_fr
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int dy = dy_lo + wave; dy < dy_hi; dy += NI_THREADS / 64) {
     int y0, y1, b0, b1;
-    ni_linear_coef(dy, D.scale_y, sh, y0, y1, b0, b1);
+    cv_linear_coef(dy, D.scale_y, sh, y0, y1, b0, b1);
     // the staged rows of the two source rows, each where its global address put it
     const uint8_t* l0 = luma + (y0 - y_lo) * lrow + ((unsigned)(uintptr_t)(f_luma + (long long)y0 * F.pitch) & 15u);
     const uint8_t* l1 = luma + (y1 - y_lo) * lrow + ((unsigned)(uintptr_t)(f_luma + (long long)y1 * F.pitch) & 15u);
@@ -306,27 +265,23 @@ __global__ __launch_bounds__(NI_THREADS) void nv12_resize_gather2_kernel(avsi_fr
     const uint8_t* c1 = chroma + ((y1 >> 1) - c_lo) * lrow + ((unsigned)(uintptr_t)(f_chroma + (long long)(y1 >> 1) * F.pitch) & 15u);
     uint8_t* o = out + (dy - dy_lo) * row_out;
     for (int dx = lane; dx < dw; dx += 64) {
-      const uint2 cf = coef[dx];
-      const int x0 = (int)(cf.x & 0xffffu), x1 = (int)(cf.x >> 16);
-      const int a0 = (int)(cf.y & 0xffffu), a1 = (int)(cf.y >> 16);
+      int x0, x1, a0, a1;
+      cv_coef_at(coef, dx, x0, x1, a0, a1);
       const int u0 = x0 & ~1, u1 = x1 & ~1;
+      // a chroma pair through one pointer: its second byte is then the first one's address with an offset of 1,
+      // whatever the compiler makes of an even index plus 1
+      const uint8_t *q00 = c0 + u0, *q01 = c0 + u1, *q10 = c1 + u0, *q11 = c1 + u1;
       int p00[3], p01[3], p10[3], p11[3];
-      avsi_yuv2bgr(F.m, l0[x0], c0[u0], c0[u0 + 1], p00[0], p00[1], p00[2]);
-      avsi_yuv2bgr(F.m, l0[x1], c0[u1], c0[u1 + 1], p01[0], p01[1], p01[2]);
-      avsi_yuv2bgr(F.m, l1[x0], c1[u0], c1[u0 + 1], p10[0], p10[1], p10[2]);
-      avsi_yuv2bgr(F.m, l1[x1], c1[u1], c1[u1 + 1], p11[0], p11[1], p11[2]);
+      avsi_yuv2bgr(F.m, l0[x0], q00[0], q00[1], p00[0], p00[1], p00[2]);
+      avsi_yuv2bgr(F.m, l0[x1], q01[0], q01[1], p01[0], p01[1], p01[2]);
+      avsi_yuv2bgr(F.m, l1[x0], q10[0], q10[1], p10[0], p10[1], p10[2]);
+      avsi_yuv2bgr(F.m, l1[x1], q11[0], q11[1], p11[0], p11[1], p11[2]);
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int S0 = p00[c] * a0 + p01[c] * a1;
-        const int S1 = p10[c] * a0 + p11[c] * a1;
-        int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        o[dx * 3 + c] = (uint8_t)v;
-      }
+      for (int c = 0; c < 3; ++c) o[dx * 3 + c] = cv_blend(p00[c], p01[c], p10[c], p11[c], a0, a1, b0, b1);
     }
   }
   __syncthreads();
-  ni_stage_out(g_out, out, (dy_hi - dy_lo) * row_out);
+  stage_out<NI_THREADS>(g_out, out, (dy_hi - dy_lo) * row_out);
 }
 
 // the band and the LDS rows of one destination: the most luma rows and the most chroma rows any band of `band` output
@@ -336,11 +291,8 @@ static size_t ni_plan(ni_dest& D, int sh, int sw) {
   for (int band = AVSI_RESIZE_BAND; band >= 1; band >>= 1) {
     int nl = 1, nc = 1;
     for (int lo = 0; lo < D.dh; lo += band) {
-      float f;
-      const int hi = lo + band < D.dh ? lo + band : D.dh;
-      const int y_lo = ni_src_pos(lo, D.scale_y, sh, f);
-      int y_hi = ni_src_pos(hi - 1, D.scale_y, sh, f) + 1;
-      if (y_hi > sh - 1) y_hi = sh - 1;
+      int y_lo, y_hi;
+      cv_band_rows(lo, lo + band < D.dh ? lo + band : D.dh, D.scale_y, sh, y_lo, y_hi);
       if (y_hi - y_lo + 1 > nl) nl = y_hi - y_lo + 1;
       if ((y_hi >> 1) - (y_lo >> 1) + 1 > nc) nc = (y_hi >> 1) - (y_lo >> 1) + 1;
     }
@@ -409,14 +361,21 @@ extern "C" int avsi_nv12_resize_gather2_u8(const uint8_t* d_src, int64_t n, int 
 }
 
 // ---------------------------------------------------------------------------
-// 3. |dH|, |dS|, |dV| sums of every frame against the previous frame of its video: hsv_frame_diff_batch_kernel
-// (shots_batch.hip) - the frame on grid x, a frame's strided pixels split over grid y, the first frame of every video
-// left at the memset's zeros - with both pixels converted from NV12 on the way in.
+// 3. |dH|, |dS|, |dV| sums of every frame against the previous frame of its video: hsv_diff_body (pixel_bodies.h), the
+// one text hsv_frame_diff_batch_kernel (shots_batch.hip) runs too - the frame on grid x, a frame's strided pixels split
+// over grid y, the first frame of every video left at the memset's zeros - with both pixels converted from NV12 on the
+// way in.
 // ---------------------------------------------------------------------------
+struct ni_nv12_src {   // hsv_diff_body's pixel source: a luma byte and a chroma pair, converted
+  const avsi_frames& F;
+  __device__ __forceinline__ void bgr(const uint8_t* frame, int y, int x, int& b, int& g, int& r) const {
+    avsi_pixel(F, frame, y, x, b, g, r);
+  }
+};
+
 __global__ __launch_bounds__(NI_THREADS) void nv12_hsv_diff_batch_kernel(avsi_frames F, int step, int ph, int pw,
                                                                          const long long* __restrict__ offsets, int nvideos,
                                                                          unsigned* __restrict__ sums) {
-  __shared__ unsigned red[NI_THREADS / 64][3];
   const long long f = (long long)blockIdx.x + 1;  // frame f against frame f-1
   // the video of f: the last v with offsets[v] <= f (block-uniform)
   int lo = 0, hi = nvideos;
@@ -430,35 +389,7 @@ __global__ __launch_bounds__(NI_THREADS) void nv12_hsv_diff_batch_kernel(avsi_fr
   if (offsets[lo] == f) return;  // a video's first frame: no predecessor, the memset's zeros stay
   const uint8_t* cur = F.src + f * F.frame_stride;
   const uint8_t* prv = cur - F.frame_stride;
-  unsigned a0 = 0, a1 = 0, a2 = 0;
-  const int npx = ph * pw;
-  for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < npx; i += gridDim.y * blockDim.x) {
-    const int y = (i / pw) * step, x = (i % pw) * step;
-    int b, g, r, h1, s1, v1, h0, s0, v0;
-    avsi_pixel(F, cur, y, x, b, g, r);
-    bgr2hsv_u8(b, g, r, h1, s1, v1);
-    avsi_pixel(F, prv, y, x, b, g, r);
-    bgr2hsv_u8(b, g, r, h0, s0, v0);
-    a0 += (unsigned)abs(h1 - h0);
-    a1 += (unsigned)abs(s1 - s0);
-    a2 += (unsigned)abs(v1 - v0);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a0 += __shfl_xor(a0, o, 64);
-    a1 += __shfl_xor(a1, o, 64);
-    a2 += __shfl_xor(a2, o, 64);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[wave][0] = a0;
-    red[wave][1] = a1;
-    red[wave][2] = a2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3)
-    atomicAdd(sums + f * 3 + threadIdx.x,
-              red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+  hsv_diff_body<NI_THREADS>(ni_nv12_src{F}, cur, prv, step, ph, pw, blockIdx.y, gridDim.y, sums + f * 3);
 }
 
 extern "C" int avsi_nv12_hsv_diff_batch_u8(const uint8_t* d_src, int64_t n, int h, int w, int pitch, int64_t frame_stride,

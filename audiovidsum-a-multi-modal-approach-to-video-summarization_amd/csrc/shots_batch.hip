@@ -5,6 +5,7 @@
 // (trusted: ops.ShotTables guarantees it).  Integers and fixed orders throughout: no atomics apart from the integer
 // ones of the frame-difference sums, so two calls give the same bytes.
 #include "avs_internal.h"
+#include "pixel_bodies.h"
 
 #define SB_THREADS 256
 // most workgroups on grid x: a launch holds at most 2^32 - 1 threads per grid dimension (blocks x SB_THREADS)
@@ -16,15 +17,14 @@
 #define SB_MICRO AVS_SHOT_MICRO_BATCH       // MICRO_BATCH
 
 // ---------------------------------------------------------------------------
-// 1. |dH|, |dS|, |dV| sums of every frame against the previous frame OF ITS VIDEO: the arithmetic of
-// hsv_frame_diff_kernel (visual.hip) with the frame on grid x (SB_MAX_GRID_X = 16 777 215 blocks) instead of y
-// (65 535), and the first frame of every video left at zero.
+// 1. |dH|, |dS|, |dV| sums of every frame against the previous frame OF ITS VIDEO: hsv_diff_body (pixel_bodies.h), the
+// one text hsv_frame_diff_kernel (visual.hip) runs too, with the frame on grid x (SB_MAX_GRID_X = 16 777 215 blocks)
+// instead of y (65 535), and the first frame of every video left at zero.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(SB_THREADS) void hsv_frame_diff_batch_kernel(const uint8_t* __restrict__ frames, int h, int w,
                                                                          int step, int ph, int pw,
                                                                          const long long* __restrict__ offsets, int nvideos,
                                                                          unsigned* __restrict__ sums) {
-  __shared__ unsigned red[SB_THREADS / 64][3];
   const long long f = (long long)blockIdx.x + 1;  // frame f against frame f-1
   // the video of f: the last v with offsets[v] <= f (block-uniform; V + 1 offsets, all in cache after the first block)
   int lo = 0, hi = nvideos;
@@ -38,34 +38,7 @@ __global__ __launch_bounds__(SB_THREADS) void hsv_frame_diff_batch_kernel(const 
   if (offsets[lo] == f) return;  // a video's first frame: no predecessor, the memset's zeros stay
   const uint8_t* cur = frames + f * h * (long long)w * 3;
   const uint8_t* prv = cur - (long long)h * w * 3;
-  unsigned a0 = 0, a1 = 0, a2 = 0;
-  const int npx = ph * pw;
-  for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < npx; i += gridDim.y * blockDim.x) {
-    const int y = (i / pw) * step, x = (i % pw) * step;
-    const long long o = ((long long)y * w + x) * 3;
-    int h1, s1, v1, h0, s0, v0;
-    bgr2hsv_u8(cur[o], cur[o + 1], cur[o + 2], h1, s1, v1);
-    bgr2hsv_u8(prv[o], prv[o + 1], prv[o + 2], h0, s0, v0);
-    a0 += (unsigned)abs(h1 - h0);
-    a1 += (unsigned)abs(s1 - s0);
-    a2 += (unsigned)abs(v1 - v0);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a0 += __shfl_xor(a0, o, 64);
-    a1 += __shfl_xor(a1, o, 64);
-    a2 += __shfl_xor(a2, o, 64);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[wave][0] = a0;
-    red[wave][1] = a1;
-    red[wave][2] = a2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3)
-    atomicAdd(sums + f * 3 + threadIdx.x,
-              red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+  hsv_diff_body<SB_THREADS>(bgr_dense_src{w}, cur, prv, step, ph, pw, blockIdx.y, gridDim.y, sums + f * 3);
 }
 
 extern "C" int avs_hsv_frame_diff_batch_u8(const uint8_t* d_frames, int64_t n, int h, int w, int step,

@@ -6,6 +6,7 @@
 //      pass order.
 // Integers or a fixed summation order throughout: two calls give the same bytes.
 #include "avs_internal.h"
+#include "pixel_bodies.h"
 
 #define RG_THREADS 256
 #define RG_BAND 8                     // output rows of one workgroup (halved until the source rows fit RG_LDS_BYTES)
@@ -13,33 +14,10 @@
 #define RG_INFLIGHT 4                 // 16-byte loads a lane keeps in flight while staging (as gather_rows_kernel)
 
 // ---------------------------------------------------------------------------
-// 1. cv2.resize(..., INTER_LINEAR) of gathered frames.  The arithmetic is resize_bilinear_kernel's (visual.hip), value
-// for value: rg_src_pos is the first half of its cv_linear_coef (the source position and fraction of a destination
-// index), shared with the host, which sizes the LDS by the exact row span of a band.
+// 1. cv2.resize(..., INTER_LINEAR) of gathered frames.  The arithmetic is pixel_bodies.h's, the one text
+// resize_bilinear_kernel (visual.hip) runs too: coefficients, blend, column table, and cv_band_rows, by which the host
+// sizes the LDS to the exact row span of a band and the kernel stages that span.
 // ---------------------------------------------------------------------------
-__host__ __device__ __forceinline__ int rg_src_pos(int d, double scale, int smax, float& f) {
-  f = (float)((d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (s < 0) {
-    f = 0.f;
-    s = 0;
-  }
-  if (s >= smax - 1) {
-    f = 0.f;
-    s = smax - 1;
-  }
-  return s;
-}
-
-__device__ __forceinline__ void rg_linear_coef(int d, double scale, int smax, int& s0, int& s1, int& c0, int& c1) {
-  float f;
-  s0 = rg_src_pos(d, scale, smax, f);
-  s1 = min(s0 + 1, smax - 1);
-  c0 = __float2int_rn((1.f - f) * 2048.f);
-  c1 = __float2int_rn(f * 2048.f);
-}
-
 struct rg_dest {
   uint8_t* dst;       // [count, dh, dw, 3]
   int dh, dw, band;   // band: output rows per workgroup
@@ -73,20 +51,6 @@ __device__ __forceinline__ void rg_stage_in(uint8_t* l, const uint8_t* g, int n)
   }
 }
 
-// the same cut for the way out: bytes [0, n) of `l` to `g`
-__device__ __forceinline__ void rg_stage_out(uint8_t* g, const uint8_t* l, int n) {
-  const int head = min(n, (int)((16u - (unsigned)(uintptr_t)g) & 15u));
-  const int nvec = (n - head) >> 4;
-  uint4* gv = reinterpret_cast<uint4*>(g + head);
-  const uint4* lv = reinterpret_cast<const uint4*>(l + head);
-  for (int j = threadIdx.x; j < nvec; j += RG_THREADS) gv[j] = lv[j];
-  const int tail0 = head + (nvec << 4);
-  for (int k = threadIdx.x; k < head + n - tail0; k += RG_THREADS) {
-    const int o = k < head ? k : tail0 + (k - head);
-    g[o] = l[o];
-  }
-}
-
 // grid (row of the index, band of output rows, destination).  A workgroup: (a) the column coefficients of its
 // destination, once, into LDS; (b) the source rows its band reads - one contiguous byte range of the frame - into LDS
 // with 16-byte loads; (c) one wave per output row, a lane per pixel, LDS to LDS; (d) the band's output rows - one
@@ -108,14 +72,9 @@ __global__ __launch_bounds__(RG_THREADS) void resize_gather2_kernel(const uint8_
   uint8_t* in_base = rg_lds + ((dw * 8 + 15) & ~15);
   uint8_t* out_base = in_base + D.in_bytes;
 
-  for (int dx = threadIdx.x; dx < dw; dx += RG_THREADS) {
-    int x0, x1, a0, a1;
-    rg_linear_coef(dx, D.scale_x, sw, x0, x1, a0, a1);
-    coef[dx] = make_uint2((unsigned)x0 | ((unsigned)x1 << 16), (unsigned)a0 | ((unsigned)a1 << 16));
-  }
-  float fy;
-  const int y_lo = rg_src_pos(dy_lo, D.scale_y, sh, fy);
-  const int y_hi = min(rg_src_pos(dy_hi - 1, D.scale_y, sh, fy) + 1, sh - 1);
+  cv_coef_fill<RG_THREADS>(coef, dw, D.scale_x, sw);
+  int y_lo, y_hi;
+  cv_band_rows(dy_lo, dy_hi, D.scale_y, sh, y_lo, y_hi);
   const uint8_t* g_in = src + (r * sh + y_lo) * (long long)row_in;
   uint8_t* in = in_base + ((unsigned)(uintptr_t)g_in & 15u);
   rg_stage_in(in, g_in, (y_hi - y_lo + 1) * row_in);
@@ -126,26 +85,21 @@ __global__ __launch_bounds__(RG_THREADS) void resize_gather2_kernel(const uint8_
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int dy = dy_lo + wave; dy < dy_hi; dy += RG_THREADS / 64) {
     int y0, y1, b0, b1;
-    rg_linear_coef(dy, D.scale_y, sh, y0, y1, b0, b1);
+    cv_linear_coef(dy, D.scale_y, sh, y0, y1, b0, b1);
     const uint8_t* r0 = in + (y0 - y_lo) * row_in;
     const uint8_t* r1 = in + (y1 - y_lo) * row_in;
     uint8_t* o = out + (dy - dy_lo) * row_out;
     for (int dx = lane; dx < dw; dx += 64) {
-      const uint2 cf = coef[dx];
-      const int x0 = (int)(cf.x & 0xffffu) * 3, x1 = (int)(cf.x >> 16) * 3;
-      const int a0 = (int)(cf.y & 0xffffu), a1 = (int)(cf.y >> 16);
+      int x0, x1, a0, a1;
+      cv_coef_at(coef, dx, x0, x1, a0, a1);
+      x0 *= 3, x1 *= 3;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int S0 = r0[x0 + c] * a0 + r0[x1 + c] * a1;
-        const int S1 = r1[x0 + c] * a0 + r1[x1 + c] * a1;
-        int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        o[dx * 3 + c] = (uint8_t)v;
-      }
+      for (int c = 0; c < 3; ++c)
+        o[dx * 3 + c] = cv_blend(r0[x0 + c], r0[x1 + c], r1[x0 + c], r1[x1 + c], a0, a1, b0, b1);
     }
   }
   __syncthreads();
-  rg_stage_out(g_out, out, (dy_hi - dy_lo) * row_out);
+  stage_out<RG_THREADS>(g_out, out, (dy_hi - dy_lo) * row_out);
 }
 
 // the band and the LDS bytes of one destination: the most source rows any band of `band` output rows reads, by the
@@ -155,11 +109,8 @@ static size_t rg_plan(rg_dest& D, int sh, int sw) {
   for (int band = RG_BAND; band >= 1; band >>= 1) {
     int span = 1;
     for (int lo = 0; lo < D.dh; lo += band) {
-      float f;
-      const int hi = lo + band < D.dh ? lo + band : D.dh;
-      const int y_lo = rg_src_pos(lo, D.scale_y, sh, f);
-      int y_hi = rg_src_pos(hi - 1, D.scale_y, sh, f) + 1;
-      if (y_hi > sh - 1) y_hi = sh - 1;
+      int y_lo, y_hi;
+      cv_band_rows(lo, lo + band < D.dh ? lo + band : D.dh, D.scale_y, sh, y_lo, y_hi);
       if (y_hi - y_lo + 1 > span) span = y_hi - y_lo + 1;
     }
     const size_t in_bytes = ((size_t)span * sw * 3 + 16 + 15) & ~(size_t)15;

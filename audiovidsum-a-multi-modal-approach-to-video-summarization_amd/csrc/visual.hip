@@ -1,6 +1,7 @@
 // Visual front-end kernels: all HBM-bound, one pass
 // over their tensor, 16-byte accesses along the channel axis of NHWC.
 #include "avs_internal.h"
+#include "pixel_bodies.h"
 #include <math.h>
 
 // ---------------------------------------------------------------------------
@@ -233,26 +234,8 @@ extern "C" int avs_frames_normalize_u8(int dtype, const uint8_t* d_src, int n, i
 // coefficient rounding, the >> 4 and >> 16 truncations, the final rounding) of the float64 bilinear resize with
 // half-pixel centres, and equals a 32-bit CPU restatement (tests/pixel_f64_inputs.py: resize_bound,
 // tests/test_gpu_pixel_f64.py).  What still rests on memory: bit parity with OpenCV itself [3P-memory: OpenCV source
-// absent here].
+// absent here].  The coefficients and the blend are pixel_bodies.h's, shared with the two gather kernels.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void cv_linear_coef(int d, double scale, int smax, int& s0, int& s1, int& c0, int& c1) {
-  float f = (float)((d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (s < 0) {
-    f = 0.f;
-    s = 0;
-  }
-  if (s >= smax - 1) {
-    f = 0.f;
-    s = smax - 1;
-  }
-  s0 = s;
-  s1 = min(s + 1, smax - 1);
-  c0 = __float2int_rn((1.f - f) * 2048.f);
-  c1 = __float2int_rn(f * 2048.f);
-}
-
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const uint8_t* __restrict__ src, int n, int sh, int sw,
                                                               uint8_t* __restrict__ dst, int dh, int dw,
                                                               double scale_y, double scale_x) {
@@ -270,13 +253,8 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const uint8_t* __r
     const uint8_t* r1 = src + (img * sh + y1) * (long long)sw * 3;
     uint8_t* o = dst + i * 3;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int S0 = r0[x0 * 3 + c] * a0 + r0[x1 * 3 + c] * a1;
-      const int S1 = r1[x0 * 3 + c] * a0 + r1[x1 * 3 + c] * a1;
-      int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-      v = v < 0 ? 0 : (v > 255 ? 255 : v);
-      o[c] = (uint8_t)v;
-    }
+    for (int c = 0; c < 3; ++c)
+      o[c] = cv_blend(r0[x0 * 3 + c], r0[x1 * 3 + c], r1[x0 * 3 + c], r1[x1 * 3 + c], a0, a1, b0, b1);
   }
 }
 
@@ -903,42 +881,15 @@ extern "C" int avs_segment_mean_f32(const float* d_x, int64_t ldx, int d, const 
 // (H in [0,180), 12-bit fixed-point division tables) [3P-memory: cv2 / scenedetect sources absent here].
 // Integer arithmetic end to end (block reduction by wave shuffle, one integer atomic per block), so the sums are
 // exact and order-independent.  `step` = PySceneDetect's downscale stride (frame[::step, ::step]).
-// bgr2hsv_u8 lives in avs_internal.h: shots_batch.hip's batched form of this kernel shares it.
+// The scan itself is hsv_diff_body (pixel_bodies.h), shared with shots_batch.hip's batched form and ingest.hip's NV12
+// form; here the frame is on grid y and a frame's pixels are split over grid x.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void hsv_frame_diff_kernel(const uint8_t* __restrict__ frames, int h, int w,
                                                              int step, int ph, int pw, unsigned* __restrict__ sums) {
-  __shared__ unsigned red[4][3];
   const long long f = blockIdx.y + 1;  // frame f against frame f-1
   const uint8_t* cur = frames + f * h * (long long)w * 3;
   const uint8_t* prv = cur - (long long)h * w * 3;
-  unsigned a0 = 0, a1 = 0, a2 = 0;
-  const int npx = ph * pw;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += gridDim.x * blockDim.x) {
-    const int y = (i / pw) * step, x = (i % pw) * step;
-    const long long o = ((long long)y * w + x) * 3;
-    int h1, s1, v1, h0, s0, v0;
-    bgr2hsv_u8(cur[o], cur[o + 1], cur[o + 2], h1, s1, v1);
-    bgr2hsv_u8(prv[o], prv[o + 1], prv[o + 2], h0, s0, v0);
-    a0 += (unsigned)abs(h1 - h0);
-    a1 += (unsigned)abs(s1 - s0);
-    a2 += (unsigned)abs(v1 - v0);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a0 += __shfl_xor(a0, o, 64);
-    a1 += __shfl_xor(a1, o, 64);
-    a2 += __shfl_xor(a2, o, 64);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[wave][0] = a0;
-    red[wave][1] = a1;
-    red[wave][2] = a2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3)
-    atomicAdd(sums + f * 3 + threadIdx.x,
-              red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+  hsv_diff_body<256>(bgr_dense_src{w}, cur, prv, step, ph, pw, blockIdx.x, gridDim.x, sums + f * 3);
 }
 
 extern "C" int avs_hsv_frame_diff_u8(const uint8_t* d_frames, int n, int h, int w, int step, uint32_t* d_sums,

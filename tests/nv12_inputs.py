@@ -18,7 +18,7 @@ import functools
 import numpy as np
 
 from avsum_amd import ingest
-from pixel_f64_inputs import SENTINEL_U8, source_rows  # noqa: F401  (one restatement of rg_src_pos, shared)
+from pixel_f64_inputs import SENTINEL_U8, source_rows  # noqa: F401  (one restatement of cv_src_pos, shared)
 
 BOUND = 0.5 + 493 * 2.0 ** -21     # |integer definition - float formula|: three coefficients each within 1/2 of c * 2^20,
 #                                    times at most 239, 127 and 127 (|Y - 16|, |U - 128|, |V - 128|), over 2^20; + 1/2 of
@@ -140,8 +140,8 @@ def resize_case(name):
 
 
 def resize_plan(sh, sw, dh, dw):
-    """ni_plan (ingest.hip): (band, LDS bytes, most luma rows, most chroma rows) of one destination; band 0 when even
-    one output row does not fit."""
+    """ni_plan (ingest.hip; a band's source rows by cv_band_rows of pixel_bodies.h): (band, LDS bytes, most luma rows,
+    most chroma rows) of one destination; band 0 when even one output row does not fit."""
     rows = source_rows(dh, sh)
     lrow = ((sw + 15) & ~15) + 16
     band = RESIZE_BAND

@@ -129,8 +129,8 @@ def resize_reference(frames, dh, dw):
 
 
 def resize_coefs(dn, sn, scale=None, mistake=None):
-    """cv_linear_coef (visual.hip) / rg_linear_coef (stage1_batch.hip) for every destination index: (s0, s1, c0, c1)
-    int64 [dn].  The position in fp32, the fraction by an exact fp32 subtraction, both coefficients rounded to 11 bits."""
+    """cv_linear_coef (pixel_bodies.h, the one text of all three resize kernels) for every destination index:
+    (s0, s1, c0, c1) int64 [dn].  The position in fp32, the fraction by an exact fp32 subtraction, both coefficients rounded to 11 bits."""
     scale = 1.0 / (dn / sn) if scale is None else scale
     d = np.arange(dn)
     f = (d * scale if mistake == "no_half_pixel" else (d + 0.5) * scale - 0.5).astype(F32)
@@ -148,7 +148,7 @@ def resize_coefs(dn, sn, scale=None, mistake=None):
 
 
 def source_rows(dn, sn):
-    """rg_src_pos for every destination index: the first source row of each."""
+    """cv_src_pos (pixel_bodies.h) for every destination index: the first source row of each."""
     return resize_coefs(dn, sn)[0]
 
 
@@ -207,8 +207,8 @@ def resize_bound(sh, sw):
 
 
 def gather_plan(sh, sw, dh, dw):
-    """rg_plan (stage1_batch.hip): (band, LDS bytes, most source rows a band reads) of one destination; band 0 when
-    even one output row does not fit."""
+    """rg_plan (stage1_batch.hip; a band's source rows by cv_band_rows of pixel_bodies.h): (band, LDS bytes, most source
+    rows a band reads) of one destination; band 0 when even one output row does not fit."""
     rows = source_rows(dh, sh)
     band = RG_BAND
     while band >= 1:

@@ -271,6 +271,29 @@ def test_launch_constants_match_the_sources():
     assert "const long long stride = (long long)gridDim.x * 256;" in visual and "i + 3 * stride < n16; i += 4 * stride" in visual
 
 
+def test_the_pixel_arithmetic_has_one_text():
+    """The resize arithmetic and the shot scan stand once, in pixel_bodies.h, and the kernels call them: no file of csrc/
+    holds a copy of its own.  (Sharing took csrc/ from 13 310 lines to 13 275; the count is not asserted, since the next
+    kernel added there would trip it.)"""
+    sources = {p.name: p.read_text() for p in sorted(CSRC.iterdir()) if p.is_file()}
+    once = {"source position": r"\(d \+ 0\.5\) \* scale - 0\.5", "blend": r">> 16\) \+ 2\) >> 2",
+            "wave reduction": r"__shfl_xor\(a0", "stage_out": r"^[^/\n]*\bvoid \w*stage_out\("}
+    for what, pattern in once.items():
+        found = {name: len(re.findall(pattern, text, flags=re.M)) for name, text in sources.items()}
+        assert {name: n for name, n in found.items() if n} == {"pixel_bodies.h": 1}, (what, found)
+    hips = ("visual.hip", "stage1_batch.hip", "shots_batch.hip", "ingest.hip")
+    assert all('#include "pixel_bodies.h"' in sources[f] for f in hips)
+    assert sources["pixel_bodies.h"].count("#pragma once") == 1 and '#include "avs_internal.h"' in sources["pixel_bodies.h"]
+    assert all(re.search(r"\bcv_blend\(", sources[f]) for f in ("visual.hip", "stage1_batch.hip", "ingest.hip"))
+    assert all(len(re.findall(r"\bhsv_diff_body<", sources[f])) == 1 for f in ("visual.hip", "shots_batch.hip", "ingest.hip"))
+    for name, plan in (("stage1_batch.hip", "rg_plan"), ("ingest.hip", "ni_plan")):
+        body = re.search(r"^static size_t " + plan + r"\(.*?\n}\n", sources[name], flags=re.S | re.M)
+        assert body and "cv_band_rows(" in body.group(0), plan
+    # nothing in the header has external linkage: every function at file scope is force-inlined
+    starts = [ln for ln in sources["pixel_bodies.h"].splitlines() if "(" in ln and re.match(r"[A-Za-z_]", ln)]
+    assert len(starts) >= 8 and all(re.match(r"(__host__ )?__device__ __forceinline__ ", ln) for ln in starts), starts
+
+
 def test_the_cases_reach_every_path():
     # resize: one trip at every pair, the second at the 65 537-frame case and not one frame earlier
     big = pfi.RESIZE_BIG
