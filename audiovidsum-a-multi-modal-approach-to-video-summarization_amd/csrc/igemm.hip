@@ -88,7 +88,12 @@ __device__ __forceinline__ void avs_split_bf16(const float4& p0, const float4& p
 //   EPI_AFFINE AVS_F16X2, 1x1 convolutions: a folded BatchNorm affine GIVEN per group of rows (computed beforehand from
 //              the input's Gram matrix, avs_bn_gram_affine_f16x2) + residual + ReLU: the one streaming pass of the
 //              expanding 1x1 layers whose groups are too large for a tile.  256-row tiles; 128-row tiles (three
-//              workgroups per CU) for wide outputs of reductions up to 128 channels
+//              workgroups per CU) for wide outputs of reductions up to 128 channels.  Two instantiations: the general one
+//              keeps the affines of the up to three groups a wave's 64 rows can lie in and picks one per value (two
+//              compares, two selects per scale and shift); GROUPW, which the plan takes when rows_per_group is a multiple
+//              of 64 (the trunk's 56 x 56 and 28 x 28 maps): a wave's rows start at a multiple of 64, so the wave lies in
+//              ONE group - one (scale, shift) per column tile, no selects, and the residual's own affine (p.res_scale)
+//              loaded once per tile instead of per run behind a 64-bit division.  The same fmaf per value: the same bits
 
 // PIPE: three operand buffers, the DMA of step s+2 is issued in step s; fragment reads are inline-asm
 // ds_read_b128 and the waits are hand-counted (s_waitcnt vmcnt(N) + raw s_barrier), because hipcc orders every
@@ -130,8 +135,13 @@ __device__ __forceinline__ void avs_split_bf16(const float4& p0, const float4& p
 // and the nine taps read the finished values: the apply pass over the input (a read and a write of it in HBM) disappears.
 // The zero rows the padding taps read stay zero (the padding belongs to the finished activation), so the products, the
 // outputs and the statistics are those of avs_bn_apply followed by the plain form, bit for bit.
+// Which group a buffer row belongs to is answered in one of two ways.  Groups of at least 384 rows and cin <= 128
+// (p.xin_table; every group of the trunk's layers 1-2): a tile's 384 buffer rows touch at most two groups, whose (scale,
+// shift) rows are copied into a 2 x cin x 2-float LDS table once per tile; the rewrite then reads its values and its
+// table row together and has no division and no global load (xin_block_tab).  Smaller groups or wider inputs: a division
+// and four 16-byte loads from L2 per (row, run) pair (xin_block).  The arithmetic per value is the same.
 template <int ES, int BN, bool ACC64, bool SPATIAL, int ROWB, int EPI, bool PIPE, int WR = 2, bool FASTK = false,
-          int SPLIT = 0, bool TAP9 = false, bool AP8 = false, bool XIN = false>
+          int SPLIT = 0, bool TAP9 = false, bool AP8 = false, bool XIN = false, bool GROUPW = false>
 __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64 && ES == 2) ? 4 : 3) : 2) void igemm_kernel(
     IgemmParams p) {
   static_assert(!AP8 || (SPLIT == 2 && ES == 4 && PIPE && ROWB == 64 && FASTK && !SPATIAL && !TAP9 && EPI == EPI_STATS),
@@ -141,6 +151,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
                 "the shifted-row form: AVS_F16X2 / bf16 convolution + statistics / tile-local BatchNorm (3x3), AVS_F16X2 bias + "
                 "ReLU (any stride-1 'same' filter) on the pipelined 256-row tiles");
   static_assert(!XIN || (TAP9 && SPLIT == 2 && EPI == EPI_STATS), "the input affine: AVS_F16X2 nine-tap convolution + statistics");
+  static_assert(!GROUPW || (EPI == EPI_AFFINE && SPLIT == 2), "a wave in one group: an instantiation of the given-affine form");
   static_assert(SPLIT == 0 || (ES == 4 && !ACC64), "the split arithmetic is for 4-byte operands");
   static_assert(WR == 2 || (WR == 4 && !ACC64 && (ES == 2 || SPLIT != 0)),
                 "256-row tiles are built for the bf16 variants and the fp32-split arithmetic");
@@ -180,7 +191,11 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
   constexpr int T9_AROWS = 384;
   constexpr int T9_ABUF = (T9_AROWS + 4) * CPRR;
   constexpr int T9_BBUF = NB * RPP * CPRR;
-  constexpr int OPERAND_SLOTS = TAP9 ? 2 * T9_ABUF + 3 * T9_BBUF : NBUF * BUF;
+  // XIN: the input affines of the (at most two) groups a tile's 384 buffer rows touch, [2][cin / 8][scale 8 | shift 8] floats,
+  // behind the operand buffers (cin <= XIN_TABLE_MAX_CIN; with it the BN = 128 form holds 76 288 of the 81 920 bytes a
+  // workgroup may have at two per CU, the BN = 64 form 64 000)
+  constexpr int XTAB_SLOTS = XIN ? (2 * XIN_TABLE_MAX_CIN * 2 * 4) / 16 : 0;
+  constexpr int OPERAND_SLOTS = (TAP9 ? 2 * T9_ABUF + 3 * T9_BBUF : NBUF * BUF) + XTAB_SLOTS;
   constexpr int LDS_BASE = OPERAND_SLOTS > CT_SLOTS + TAB_SLOTS ? OPERAND_SLOTS : CT_SLOTS + TAB_SLOTS;
   constexpr int LDS_SLOTS = LDS_BASE > H2_SLOTS ? LDS_BASE : H2_SLOTS;
 
@@ -476,6 +491,28 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
       vm[mt] = mk;
     }
     if (t < 32) lds[(t >> 4) * T9_ABUF + T9_AROWS * CPRR + (t & 15)] = make_uint4(0u, 0u, 0u, 0u);   // the rows of zeros
+    // XIN, p.xin_table (groups of at least 384 rows): the tile's 384 buffer rows touch at most two groups - g0, the group of
+    // the first row that exists, and g0 + 1 from buffer row xbnd on (>= 384: the whole tile lies in g0).  Their (scale,
+    // shift) rows are copied into LDS once, before the first block lands, laid out per run of 8 channels: scale 8 | shift 8
+    constexpr int XTAB0 = OPERAND_SLOTS - XTAB_SLOTS;
+    int xbnd = T9_AROWS;
+    if constexpr (XIN) {
+      if (p.xin_table) {
+        const long long rpg = p.rows_per_group;
+        const long long g0 = mbase / rpg, gl = ((long long)p.M - 1) / rpg;
+        const long long bnd = (g0 + 1) * rpg - ((long long)m0 - w1);
+        xbnd = bnd < T9_AROWS ? (int)bnd : T9_AROWS;
+        if (t < p.cin) {   // one float4 per thread: [group][scale | shift][cin / 4]
+          const int half = p.cin >> 1, quart = p.cin >> 2;
+          const int gsel = t / half, r = t - gsel * half;
+          const int which = r / quart, q4 = r - which * quart;
+          const long long g = g0 + gsel < gl ? g0 + gsel : gl;   // (a tile in the last group: its own rows again, never picked)
+          const float4 v = *reinterpret_cast<const float4*>((which ? p.in_shift : p.in_scale) + g * p.cin + 4 * q4);
+          float* const tab = reinterpret_cast<float*>(lds + XTAB0);
+          *reinterpret_cast<float4*>(tab + (gsel * (p.cin >> 3) + (q4 >> 1)) * 16 + which * 8 + (q4 & 1) * 4) = v;
+        }
+      }
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     unsigned fb9[NT][2];
 #pragma unroll
@@ -542,6 +579,83 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         lo = l;
       }
     };
+    // p.xin_table: the same rewrite without a division or a global load.  A thread's run of 8 channels is fixed (t & 1), so
+    // the table row of its three (hi, lo) pairs is fixed per group.  A tile that lies in one group (xbnd >= 384, nearly all
+    // of them: uniform) reads its six value chunks and the four table chunks with ds_read_b128 issued together - one LDS
+    // latency per block instead of three dependent chains through L2.  A tile with a boundary picks the table row per pair
+    // by a >= xbnd and takes the pairs one after the other (all eighteen chunks in flight at once spill the 128-column
+    // form).  Rows before row 0 and past M are skipped as in xin_block.  A halo row that belongs to a frame of the other
+    // group takes that group's affine (its own); no tap inside a frame reads such a row, so either group's would do.
+    auto xin_block_tab = [&](int b) {
+      constexpr int NP = (T9_AROWS * 2) / 256;
+      const int run = t & 1;
+      const unsigned ab = lds_base + (unsigned)(b & 1) * (T9_ABUF * 16u);
+      const unsigned tb = lds_base + (unsigned)XTAB0 * 16u + (unsigned)(2 * b + run) * 64u;
+      const unsigned tg = (unsigned)p.cin * 8u;   // bytes from group g0's table to the next group's
+      unsigned ha[NP];
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        const int a = (t >> 1) + 128 * i;
+        ha[i] = ab + (unsigned)(a * CPRR + ((2 * run) ^ ((a >> SH) & (CPRR - 1)))) * 16u;
+      }
+      // one pair: join, v * scale + shift, ReLU, split, back into its two chunks; tv = scale 0-3 | 4-7 | shift 0-3 | 4-7
+      auto finish = [&](int i, const uint4& hi, const uint4& lo, const uint4 (&tv)[4]) {
+        const int m = m0 - w1 + (t >> 1) + 128 * i;
+        if (m < 0 || m >= p.M) return;
+        float v[8];
+        avs_f16x2_join8(hi, lo, v);
+        const float4 s0 = __builtin_bit_cast(float4, tv[0]), s1 = __builtin_bit_cast(float4, tv[1]);
+        const float4 f0 = __builtin_bit_cast(float4, tv[2]), f1 = __builtin_bit_cast(float4, tv[3]);
+        const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+        const float sf[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[j] + sf[j];
+        if (p.in_relu) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
+        }
+        uint4 h, l;
+        avs_f16x2_split8(v, h, l);
+        // (the lo chunk's slot is the hi chunk's with bit 0 flipped, whatever the swizzle: 16 bytes beside it)
+        *reinterpret_cast<uint4*>(reinterpret_cast<char*>(lds) + (ha[i] - lds_base)) = h;
+        *reinterpret_cast<uint4*>(reinterpret_cast<char*>(lds) + ((ha[i] ^ 16u) - lds_base)) = l;
+      };
+      uint4 hi[NP], lo[NP], tv[4];
+      if (xbnd >= T9_AROWS) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+          hi[i] = avs_lds_read_b128(ha[i]);
+          lo[i] = avs_lds_read_b128(ha[i] ^ 16u);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tv[j] = avs_lds_read_b128(tb + 16u * j);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+          avs_pin(hi[i]);
+          avs_pin(lo[i]);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) avs_pin(tv[j]);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) finish(i, hi[i], lo[i], tv);
+      } else {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+          const unsigned tp = tb + ((t >> 1) + 128 * i >= xbnd ? tg : 0u);
+          hi[0] = avs_lds_read_b128(ha[i]);
+          lo[0] = avs_lds_read_b128(ha[i] ^ 16u);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) tv[j] = avs_lds_read_b128(tp + 16u * j);
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          avs_pin(hi[0]);
+          avs_pin(lo[0]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) avs_pin(tv[j]);
+          finish(i, hi[0], lo[0], tv);
+        }
+      }
+    };
     stage_a(0, 0);
     stage_b();
     if (steps > 1) stage_b();
@@ -561,7 +675,10 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
       __builtin_amdgcn_s_barrier();
       if constexpr (XIN) {
         if (tap == 0) {   // block blk has landed (every wave's share: the barrier above); no tap has read it yet
-          xin_block(blk);
+          if (p.xin_table)
+            xin_block_tab(blk);
+          else
+            xin_block(blk);
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_s_barrier();
         }
@@ -929,7 +1046,8 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
     // 64 rows minus 4 * lh); both lane halves return the column's total over the wave's rows
     auto wave_sum = [&](int nt, int lo, int hi) -> float {
       float s = 0.f;
-      if (lo <= 0 && hi >= 64) {
+      // (lo and hi are shifted by 4 * lh: undo it, so that both lane halves take the same branch)
+      if (lo + 4 * lh <= 0 && hi + 4 * lh >= 64) {
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -947,14 +1065,24 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
     };
     auto wave_sq = [&](int nt, int lo, int hi, float mean) -> float {
       float s = 0.f;
+      if (lo + 4 * lh <= 0 && hi + 4 * lh >= 64) {   // the wave lies in one group: the same adds in the same order, no masks
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
+        for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
-          const float d = acc[mt][nt][e] - mean;
-          s = (roff >= lo && roff < hi) ? fmaf(d, d, s) : s;
-        }
+          for (int e = 0; e < 16; ++e) {
+            const float d = acc[mt][nt][e] - mean;
+            s = fmaf(d, d, s);
+          }
+      } else {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+            const float d = acc[mt][nt][e] - mean;
+            s = (roff >= lo && roff < hi) ? fmaf(d, d, s) : s;
+          }
+      }
       return s + __shfl_xor(s, 32, 64);
     };
     // per-lane BatchNorm affines of the (up to three) groups this wave's rows lie in (EPI_BNLOCAL)
@@ -1164,7 +1292,21 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
       }
       __syncthreads();   // the tables alias the staging regions
     }
-    if constexpr (EPI == EPI_AFFINE) {
+    long long wgrp = 0;   // GROUPW: the wave's one group
+    if constexpr (GROUPW) {
+      // rows_per_group is a multiple of 64 and a wave's rows start at one: the wave lies in ONE group, a lane holds one
+      // (scale, shift) per column tile and no value asks which group it is in
+      const int rpg = p.rows_per_group;
+      const int r_first = m0 + wr * 64;
+      const int gl = (p.M - 1) / rpg;                       // last group (a wave past M stores nothing)
+      wgrp = r_first / rpg < gl ? r_first / rpg : gl;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const int col = n0 + wc * WCOLS + nt * 32 + lr;
+        const bool cv = col < p.N;
+        sc0[nt] = cv ? p.gamma[wgrp * p.N + col] : 0.f, sf0[nt] = cv ? p.beta[wgrp * p.N + col] : 0.f;
+      }
+    } else if constexpr (EPI == EPI_AFFINE) {
       // the given affines of the (up to three) groups this wave's 64 rows lie in
       const int rpg = p.rows_per_group;
       const int r_first = m0 + wr * 64;
@@ -1191,12 +1333,29 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
-            const bool in1 = roff >= bnd1, in2 = roff >= bnd2;
-            const float sc = in2 ? sc2[nt] : (in1 ? sc1[nt] : sc0[nt]);
-            const float sf = in2 ? sf2[nt] : (in1 ? sf1[nt] : sf0[nt]);
-            acc[mt][nt][e] = fmaf(acc[mt][nt][e], sc, sf);
+            if constexpr (GROUPW) {
+              acc[mt][nt][e] = fmaf(acc[mt][nt][e], sc0[nt], sf0[nt]);
+            } else {
+              const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+              const bool in1 = roff >= bnd1, in2 = roff >= bnd2;
+              const float sc = in2 ? sc2[nt] : (in1 ? sc1[nt] : sc0[nt]);
+              const float sf = in2 ? sf2[nt] : (in1 ? sf1[nt] : sf0[nt]);
+              acc[mt][nt][e] = fmaf(acc[mt][nt][e], sc, sf);
+            }
           }
+    }
+    // GROUPW: the residual's affine of this lane's 8 columns, in the wave's one group: loaded once, kept across both halves
+    float ras[GROUPW ? 8 : 1], rbs[GROUPW ? 8 : 1];
+    if constexpr (GROUPW) {
+      if (p.res_scale) {
+        const long long gq = col_ok ? wgrp * p.N + col8 : 0;   // (a lane without columns reads the first run: never used)
+        const float4 a0 = *reinterpret_cast<const float4*>(p.res_scale + gq);
+        const float4 a1 = *reinterpret_cast<const float4*>(p.res_scale + gq + 4);
+        const float4 b0 = *reinterpret_cast<const float4*>(p.res_shift + gq);
+        const float4 b1 = *reinterpret_cast<const float4*>(p.res_shift + gq + 4);
+        ras[0] = a0.x, ras[1] = a0.y, ras[2] = a0.z, ras[3] = a0.w, ras[4] = a1.x, ras[5] = a1.y, ras[6] = a1.z, ras[7] = a1.w;
+        rbs[0] = b0.x, rbs[1] = b0.y, rbs[2] = b0.z, rbs[3] = b0.w, rbs[4] = b1.x, rbs[5] = b1.y, rbs[6] = b1.z, rbs[7] = b1.w;
+      }
     }
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
@@ -1239,7 +1398,12 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
             else
               avs_f16x2_join8(rhi[mt][it], rlo[mt][it], rv);
             if constexpr (EPI == EPI_AFFINE) {
-              if (p.res_scale) {   // the residual is a raw convolution output: its BatchNorm rides in the add
+              if constexpr (GROUPW) {
+                if (p.res_scale) {
+#pragma unroll
+                  for (int j = 0; j < 8; ++j) rv[j] = fmaf(rv[j], ras[j], rbs[j]);
+                }
+              } else if (p.res_scale) {   // the residual is a raw convolution output: its BatchNorm rides in the add
                 const long long gq = (row / p.rows_per_group) * p.N + col8;
                 const float4 a0 = *reinterpret_cast<const float4*>(p.res_scale + gq);
                 const float4 a1 = *reinterpret_cast<const float4*>(p.res_scale + gq + 4);
@@ -1694,6 +1858,12 @@ extern "C" void avs_tune_tall_rule(int min_tiles, int min_k_bytes) {
 }
 extern "C" void avs_tune_pipeline(int enabled) { g_pipe3 = enabled; }
 extern "C" void avs_tune_bnlocal(int enabled) { g_bnlocal = enabled; }
+// AVS_GROUP_LOOKUPS (read per call, so one process can compare): bit 0 keeps the given-affine epilogue's per-value group
+// selects where the wave-in-one-group instantiation would run, bit 1 the input transform's per-row lookups
+static int study_group_lookups() {
+  const char* e = getenv("AVS_GROUP_LOOKUPS");
+  return e ? atoi(e) : 0;
+}
 #endif
 
 // The shapes the nine-tap form takes (AVS_F16X2 convolution + statistics on the 256-row tiles): 3x3 / stride 1 / pad 1,
@@ -1842,6 +2012,12 @@ static int igemm_plan(int dtype, const IgemmParams& p, int batch, bool stats, bo
     // the 128-row form exists on 64-byte reduction steps only: a longer reduction keeps the 256-row tile whatever the caller
     // asks for (the variant is a tuning hint: results do not depend on it)
     if (!pl.tall && (long long)p.K * 4 > g_rowb_threshold_bytes) pl.tall = true;
+    // groups that are whole numbers of 64 rows: a wave's rows (they start at a multiple of 64) lie in one group, and the
+    // instantiation without the per-value group selects computes the same bits (the trunk's 56 x 56 and 28 x 28 maps)
+    pl.groupw = p.rows_per_group % 64 == 0;
+#ifdef AVS_STUDY
+    if (study_group_lookups() & 1) pl.groupw = false;
+#endif
   }
   pl.tile_rows = p.tile_rows ? p.tile_rows : (pl.tall ? 256 : 128);
   pl.tiles_m = ((long long)p.M + pl.tile_rows - 1) / pl.tile_rows;
@@ -1928,6 +2104,9 @@ static bool igemm_lift_staging(const IgemmPlan& pl, dim3 grid, hipStream_t strea
   }
   if constexpr (SPLIT == 2 && EPI == EPI_STATS && !SP && ROWB == 64 && PIPE && FK) {
     if (pl.ap8) AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI, PIPE, WR, FK, SPLIT, false, true>));
+  }
+  if constexpr (EPI == EPI_AFFINE && SPLIT == 2) {
+    if (pl.groupw) AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI, PIPE, WR, FK, SPLIT, false, false, false, true>));
   }
   AVS_LAUNCH_RET((igemm_kernel<ES, BN, ACC64, SP, ROWB, EPI, PIPE, WR, FK, SPLIT>));
 }
@@ -2032,8 +2211,11 @@ static int igemm_run(const IgemmPlan& pl, IgemmParams& p, hipStream_t stream, co
   p.tall = pl.tall;
   p.tiles_n = pl.tiles_n;
   p.lin_stride = pl.lin_stride;
+  // the input affine's group lookup: from an LDS table of the tile's two groups where a tile cannot touch a third
+  p.xin_table = pl.xin && p.rows_per_group >= XIN_TABLE_MIN_GROUP_ROWS && p.cin <= XIN_TABLE_MAX_CIN;
 #ifdef AVS_STUDY
   p.debug = g_debug_flags;
+  if (study_group_lookups() & 2) p.xin_table = 0;
 #endif
   const dim3 grid((unsigned)pl.grid, 1, (unsigned)pl.batch);
   if (pl.local224) {

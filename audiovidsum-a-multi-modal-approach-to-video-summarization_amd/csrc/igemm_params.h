@@ -71,6 +71,9 @@ struct IgemmParams {
   const float* in_scale;
   const float* in_shift;
   int in_relu;
+  // 1 (set by igemm_run from rows_per_group and cin): groups of at least XIN_TABLE_MIN_GROUP_ROWS rows - a tile's 384 buffer
+  // rows touch at most two of them, whose affines the kernel keeps in an LDS table; 0: the group is looked up per row
+  int xin_table;
 #ifdef AVS_STUDY
   int debug;  // ablation switches of the kernel-study build (tools/): 1 = skip output stores, 2 = skip A/B loads, ...
 #endif
@@ -79,6 +82,8 @@ struct IgemmParams {
 enum { EPI_PLAIN = 0, EPI_STATS = 1, EPI_ANY = 2, EPI_BRELU = 3, EPI_BNLOCAL = 5, EPI_AFFINE = 6 };
 constexpr int BNLOCAL_MAX_GROUPS = 6;  // groups per 256-row tile (rows_per_group >= 43)
 constexpr int STATS_MIN_GROUP_ROWS = 64;  // EPI_STATS: a wave's 64 rows then overlap at most two groups
+constexpr int XIN_TABLE_MIN_GROUP_ROWS = 384;  // XIN: the nine-tap form's 384 buffer rows then touch at most two groups
+constexpr int XIN_TABLE_MAX_CIN = 128;         // ... and the two groups' affines fit the LDS table (2 x cin x 2 floats)
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -126,6 +131,7 @@ struct IgemmPlan {
   bool fastk;          // the scalar tap walk
   bool tap9, ap8, xin; // the shifted-row staging, the AVS_F16P8 input, the input affine
   bool in_affine;      // the caller gives an input affine: only the XIN kernel may run
+  bool groupw;         // EPI_AFFINE: rows_per_group is a multiple of 64, so every wave's 64 rows lie in ONE group (GROUPW)
   bool local224;       // the 224-row tile takes it
   int tile_rows;       // rows of a tile that are used = the pitch between tiles
   long long tiles_m;

@@ -24,9 +24,15 @@ def main():
     for r in csv.DictReader(open(sys.argv[1])):
         full = r["Kernel_Name"].replace("void ", "")
         name = re.sub(r"<.*", "", full).split("(")[0]
+        # (a fourth trailing bool, from r08 on: GROUPW, the given-affine epilogue's wave-in-one-group instantiation)
+        gw = re.search(r"(, \d+(?:, (?:true|false)){3}), (true|false)>\(", full + "(")
+        if full.startswith("igemm_kernel<") and gw:
+            full = full.replace(gw.group(0)[:-1], gw.group(1) + ">")
         m = re.match(r"igemm_kernel<(\d+), (\d+), \w+, (\w+), (\d+), (\d+)", full)
         if m:   # element size, column tile, spatial, row bytes, epilogue form
             name = f"igemm_kernel<es={m.group(1)},bn={m.group(2)},spatial={m.group(3)},epi={m.group(5)}>"
+            if gw and gw.group(2) == "true":
+                name = name[:-1] + ",groupw>"
             last = re.search(r", (\d+)(?:, (?:true|false)){0,2}>\(", full + "(")   # (trailing bools: nine-tap form, AVS_F16P8 input)
             if m.group(1) == "4" and last and last.group(1) in ("1", "2"):
                 name = name[:-1] + f",split={last.group(1)}>"

@@ -8,10 +8,11 @@ Per layer: time per pass, matrix rate (algorithmic FLOP / time), stream rate (bf
 time) and the time an ideal kernel would take: max(FLOP / 1.2 PFLOP/s, bytes / 5.5 TB/s) - 1.2 PF is what the LDS-DMA
 intake allows a 128x128-tile contraction here, 5.5 TB/s what a streaming kernel reaches on this chip.
 
-Usage: python tools/layer_table.py [--n 8192] [--gf 1] [--dtype bf16|f32split|f16x2] [--pack on|off|ab] [--mfma 16|32|ab]"""
+Usage: python tools/layer_table.py [--n 8192] [--gf 1] [--dtype bf16|f32split|f16x2] [--pack on|off|ab] [--mfma 16|32|ab]
+       [--lookups ab]"""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-if any(a.startswith("--mfma") for a in sys.argv[1:]):
+if any(a.startswith("--mfma") or a.startswith("--lookups") for a in sys.argv[1:]):
     os.environ["AVS_STUDY_LIB"] = "1"  # the shape switch of the 224-row kernel lives in the study build only (make -C <pkg>/csrc study)
 import torch
 from avsum_amd import cnn, ops
@@ -29,6 +30,10 @@ ap.add_argument("--pack", default="on", choices=["on", "off", "ab"],
 ap.add_argument("--mfma", default="", choices=["", "16", "32", "ab"],
                 help="f16x2, study build: the 224-row kernel's matrix instruction forced to 16x16x32 / 32x32x16 (AVS_LOCAL224_MFMA), "
                      "or ab: 32, 16, 32 in one run and a comparison of its rows per instance (3x3 / 1x1)")
+ap.add_argument("--lookups", default="", choices=["", "ab"],
+                help="f16x2, study build: the per-value group lookups of layers 1-2 (AVS_GROUP_LOOKUPS: bit 0 the given-affine "
+                     "epilogue's selects, bit 1 the nine-tap input transform's per-row lookups) - ab: kept, removed, kept again "
+                     "in one run and a comparison per piece")
 ap.add_argument("--short", type=int, default=0,
                 help="study build (AVS_STUDY_LIB=1): reductions of at most this many bytes per row take 64-byte steps (rule: 2048)")
 args = ap.parse_args()
@@ -228,6 +233,35 @@ if args.mfma == "ab":
             print(f"{(str(cnt) + ' x ' + k[0]):34s} {a:9.2f} {b:9.2f} {abs(a - b) / base * 100:6.1f}% {ms:9.2f} {(ms - base) / base * 100:+6.1f}%")
         if su:
             print(f"{'sum':34s} {su:9.2f} {'':9s} {rep / su * 100:6.1f}% {sp:9.2f} {(sp - su) / su * 100:+6.1f}%")
+        print()
+elif args.lookups == "ab":
+    # general paths, the group-aligned ones, general again in ONE process: the second general table gives the repeatability.
+    # Piece A: the rows that hold a one-pass given-affine 1x1 (gram / affine forms of the 56 x 56 and 28 x 28 maps);
+    # piece B: the 3x3 statistics rows of those maps (the nine-tap form with the input affine)
+    tabs = []
+    for label, bits in (("[lookups kept, 1st] ", "3"), ("[lookups removed] ", "0"), ("[lookups kept, 2nd] ", "3")):
+        os.environ["AVS_GROUP_LOOKUPS"] = bits
+        tabs.append(measure(label))
+        print()
+    a1, new, a2 = tabs
+    maps = ("56x56 ", "28x28 ")
+    for piece, pick in (("A: one-pass given-affine 1x1", lambda k: k[1] in ("gram", "affine") and " gram " not in k[0]),
+                        ("B: nine-tap input transform", lambda k: k[1].startswith("stats") and " 3x3/1 " in k[0])):
+        print(f"{piece:34s} {'kept':>9s} {'again':>9s} {'repeat':>7s} {'removed':>9s} {'change':>7s}  (ms; kept = the faster of the two)")
+        su = sp = rep_ = 0.0
+        for k, (cnt, ms) in new.items():
+            if not k[0].startswith(maps) or not pick(k):
+                continue
+            a, b = a1[k][1], a2[k][1]
+            base = min(a, b)
+            su += base
+            sp += ms
+            rep_ += abs(a - b)
+            verdict = "" if ms - base <= abs(a - b) else "  SLOWER than the repeatability"
+            print(f"{(str(cnt) + ' x ' + k[0]):34s} {a:9.2f} {b:9.2f} {abs(a - b) / base * 100:6.1f}% {ms:9.2f} {(ms - base) / base * 100:+6.1f}%{verdict}")
+        if su:
+            print(f"{'sum':34s} {su:9.2f} {'':9s} {rep_ / su * 100:6.1f}% {sp:9.2f} {(sp - su) / su * 100:+6.1f}%"
+                  f"  keep rule: {'met' if su - sp > rep_ else 'NOT met'}")
         print()
 elif args.pack != "ab":
     if args.mfma:
