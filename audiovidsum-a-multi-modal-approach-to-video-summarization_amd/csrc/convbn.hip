@@ -16,9 +16,7 @@
 // Tile machinery = igemm.hip's (LDS-DMA staging, 64-byte rows, XOR-swizzled slots, 2 x 2 waves of
 // 64 x BN/2 outputs, v_mfma_f32_32x32x16_bf16); rows are linear (output row m reads input row m).
 #include "avs_internal.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "igemm_params.h"
 
 __device__ __attribute__((aligned(16))) unsigned int avs_zero16_cb[4];  // zero source for padded lanes
 
@@ -50,10 +48,6 @@ struct ConvBnParams {
 
 #define AVS_CONVBN_MAX_K 512
 
-#define AVS_GLDS16(src, dst)                                                                        \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),            \
-                                   (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
-
 template <int BN, bool XF, bool PRE = false, bool RA = false>
 // (Four workgroups per CU for the streaming form - 40 KB of LDS each fits - need <= 128 VGPRs: the 128-column
 //  variants then spill 11-16 registers and the kernel ran at 3.1 instead of 4.2 TB/s; three it is.)
@@ -74,9 +68,7 @@ __global__ __launch_bounds__(256, 3) void conv1x1_bn_kernel(ConvBnParams p) {
   __shared__ float red[2][BN][2];
   __shared__ __attribute__((aligned(16))) float xf[XF ? 2 : 1][XF ? AVS_CONVBN_MAX_K : 4];  // input scale | shift
 
-  const unsigned nwg = gridDim.x, orig = blockIdx.x;
-  const unsigned q = nwg >> 3, rr = nwg & 7, xcd = orig & 7;
-  const unsigned wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
+  const unsigned wg = avs_xcd_remap(gridDim.x, blockIdx.x);
   const int tn = wg % p.tiles_n;
   const int g = wg / p.tiles_n;
   const int n0 = tn * BN;
@@ -92,7 +84,7 @@ __global__ __launch_bounds__(256, 3) void conv1x1_bn_kernel(ConvBnParams p) {
   const int wave = t >> 6, lane = t & 63;
   const int c = t & (CPRR - 1);
   const int rb = t / CPRR;
-  const int cq = c ^ ((rb >> SH) & (CPRR - 1));
+  const int cq = AVS_LDS_CHUNK(CPRR, SH, rb, c);
   const int wr = wave >> 1, wc = wave & 1;
   const int lr = lane & 31, lh = lane >> 5;
 
@@ -209,12 +201,12 @@ __global__ __launch_bounds__(256, 3) void conv1x1_bn_kernel(ConvBnParams p) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
               const int row = wr * 64 + mt * 32 + lr;
-              if (mt == 0 || live > 32) fa[ks][mt] = abuf[row * CPRR + (chunk ^ ((row >> SH) & (CPRR - 1)))];
+              if (mt == 0 || live > 32) fa[ks][mt] = abuf[AVS_LDS_SLOT(CPRR, SH, row, chunk)];
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
               const int row = wc * (BN / 2) + nt * 32 + lr;
-              fb[ks][nt] = bbuf[row * CPRR + (chunk ^ ((row >> SH) & (CPRR - 1)))];
+              fb[ks][nt] = bbuf[AVS_LDS_SLOT(CPRR, SH, row, chunk)];
             }
           }
         }

@@ -43,10 +43,6 @@ __device__ __attribute__((aligned(16))) unsigned int avs_zero16[4];
 #define AVS_DEBUG_BIT(p, bit) 0
 #endif
 
-#define AVS_GLDS16(src, dst)                                                                        \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),            \
-                                   (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
-
 // AVS_F32_SPLIT: fp32 operands, arithmetic on the bf16 matrix cores.  x = hi + lo + r with hi = bf16(x), lo = bf16(x - hi),
 // |r| <= 2^-17 |x|; a*b ~ ah*bh + ah*bl + al*bh (each product exact in the fp32 accumulator), i.e. three
 // v_mfma_f32_32x32x16_bf16 per 16 reduction elements instead of eight v_mfma_f32_32x32x2_f32: 5.3x the matrix rate
@@ -67,79 +63,6 @@ __device__ __forceinline__ void avs_split_bf16(const float4& p0, const float4& p
   lo = __builtin_bit_cast(bf16x8, make_uint4(l[0], l[1], l[2], l[3]));
 }
 
-// ROWB = bytes of reduction per LDS row and step: 128 (fewer barriers per MAC; 64 KB of LDS, 2 workgroups per
-// CU) for the long reductions, 64 (32 KB, 3 workgroups per CU: more DMA in flight) for the short ones, whose
-// cost is the latency of their few loads and their stores rather than the matrix work.
-// EPI: the epilogue is what a tile of a short reduction costs, so its common forms are compiled separately:
-//   EPI_PLAIN  alpha == 1, no bias, no activation, no statistics (ResNet convolutions, projections)
-//   EPI_STATS  EPI_PLAIN + fused BatchNorm batch statistics: per-tile partial column sums in the tile's own slots
-//              (no atomics), folded in tile order by bn_fold_kernel: deterministic
-//   EPI_ANY    everything decided at run time (bias per column / row, ReLU, alpha)
-//   EPI_BRELU  alpha == 1, bias per column, ReLU (the folded-BatchNorm convolutions of Inception-v3; Linear+ReLU)
-//   EPI_BNLOCAL bf16, 256-row tiles only: the whole BatchNorm in the epilogue WITHOUT any traffic between workgroups.
-//              A tile holds floor(256 / rows_per_group) WHOLE groups (tile pitch = that many rows, the rest of the
-//              256 rows idle), so a group's statistics are sums over this tile's accumulators alone: per-wave masked
-//              column sums -> LDS across the four row-waves -> scale/shift table -> normalise (+ residual, + ReLU)
-//              -> store.  No atomics, no waiting, deterministic.  Taken when groups are at most 256 rows and fill
-//              at least 3/4 of the tile (per-frame 14x14 and 7x7 maps: 196 = 77 %, 5 x 49 = 96 %).
-// (A form in which tiles of larger groups exchanged statistics through float atomics and waited for each other inside
-//  one launch was built in round 1 and removed: results were not reproducible run to run and it only won for groups of
-//  two or three tiles, which the tile-local form covers.)
-//   EPI_AFFINE AVS_F16X2, 1x1 convolutions: a folded BatchNorm affine GIVEN per group of rows (computed beforehand from
-//              the input's Gram matrix, avs_bn_gram_affine_f16x2) + residual + ReLU: the one streaming pass of the
-//              expanding 1x1 layers whose groups are too large for a tile.  256-row tiles; 128-row tiles (three
-//              workgroups per CU) for wide outputs of reductions up to 128 channels.  Two instantiations: the general one
-//              keeps the affines of the up to three groups a wave's 64 rows can lie in and picks one per value (two
-//              compares, two selects per scale and shift); GROUPW, which the plan takes when rows_per_group is a multiple
-//              of 64 (the trunk's 56 x 56 and 28 x 28 maps): a wave's rows start at a multiple of 64, so the wave lies in
-//              ONE group - one (scale, shift) per column tile, no selects, and the residual's own affine (p.res_scale)
-//              loaded once per tile instead of per run behind a 64-bit division.  The same fmaf per value: the same bits
-
-// PIPE: three operand buffers, the DMA of step s+2 is issued in step s; fragment reads are inline-asm
-// ds_read_b128 and the waits are hand-counted (s_waitcnt vmcnt(N) + raw s_barrier), because hipcc orders every
-// LDS read it can see behind ALL outstanding LDS-DMA (vmcnt(0)), which caps a plain-HIP loop at one step of
-// prefetch.  Order per step: wait for this step's DMA -> barrier -> issue step s+2 -> read fragments -> MFMA.
-// WR: rows of waves.  2 = the 128 x BN tile (2 x 2 waves of 64 x BN/2); 4 = a 256 x BN tile (4 x 1 waves of 64 x BN):
-// twice the matrix work per barrier and 0.75 (BN = 128) instead of 1 fragment read per MFMA, for layers with many
-// rows whose cost is the loop itself (the N = 64 layers run 4 MFMAs per wave between barriers at WR = 2).
-// FASTK: cin is a multiple of one reduction step (and there are at most 32 taps), so a step never straddles a tap:
-// the tap walk (kh, kw, ci) is the same for every thread - kept in scalar registers and advanced by additions -
-// a row's padding test is one bit of a per-row tap mask built once, and a DMA source is base + scalar offset.
-// (Measured on the 3x3 layers: the general staging code issues ~180 vector + scalar instructions per 16 MFMAs and
-// the loop ran at 45 % matrix-core occupancy for that reason alone - with no staging at all it reaches 1.5 PFLOP/s.)
-// SPLIT: 0 = operands as stored; 1 = AVS_F32_SPLIT (fp32 operands split into bf16 hi + lo in the loop);
-// 2 = AVS_F16X2 (operands ARE stored as fp16 hi + lo runs: the 16-byte chunks of a step alternate hi8 | lo8, so the
-// fragments need no arithmetic at all - three v_mfma_f32_32x32x16_f16 per 16 reduction elements - and the epilogue
-// splits each output once, where it is produced, instead of every consumer splitting it per tile and step)
-// TAP9 (AVS_F16X2, 3x3 / stride 1 / pad 1 on a dense NHWC input, 256-row tiles): for output pixel (y, x) and tap (dy, dx)
-// the input pixel is row m + (dy - 1) W + (dx - 1) of the SAME flat pixel array the outputs are rows of.  So a 16-channel
-// block of the tile's pixels (+ W + 1 rows of halo on either side: 384 buffer rows) is fetched ONCE - two buffers, a
-// block ahead - and the nine taps of the block are nine reduction steps that read their A fragments from it at shifted
-// rows; a tap that leaves the frame reads a row of zeros (per-lane tap masks; this also covers tiles that straddle
-// frames).  Only the weights of a (block, tap) are fetched per step (a ring of three).  L2 -> LDS traffic of the A
-// operand / 9: for the 64-column layers, which sit at the L2 -> LDS intake ceiling (~21 B / clk / CU) with the matrix
-// cores 37 % busy.  The reduction runs block-major / tap-minor: another (fixed) summation order than the tap-major walk.
-// AP8 (AVS_F16X2 convolution + statistics, 1x1 on dense rows, 256-row tiles: conv1 of the ResNet bottlenecks in layers
-// 1-2): the input is an AVS_F16P8 tensor (fp16 hi + 8-bit remainder, 48 bytes per 16 channels).  The LDS-DMA staging is
-// the AVS_F16X2 one with other source offsets: of the four 16-byte slots of an LDS row, slot "hi 0-7" takes the block's
-// first 16 bytes, slot "hi 8-15" its second, slot "lo 0-7" the 16 remainder bytes and slot "lo 8-15" nothing (an
-// out-of-range lane), and a step advances the source by 48 instead of 64 bytes: 3 instead of 4 bytes per input value from
-// HBM, the same LDS image for the hi fragments.  A lane reads its 8 remainder bytes with one ds_read_b64 and rebuilds the
-// fp16 lo fragment in registers (5 VALU operations per value, behind the hi*hi MFMAs of the step).  (A first version
-// fetched the A fragments straight into registers - a wave owns its 64 rows for all columns on these tiles, nothing is
-// shared - with buffer_load_dwordx4 + dwordx2 per lane: 19 - 25 % SLOWER than the AVS_F16X2 path, 16-byte pieces of 32
-// rows per instruction; removed.)
-// XIN (TAP9, AVS_F16X2 convolution + statistics): the input is a RAW activation with its BatchNorm affine given per group
-// (p.in_scale / p.in_shift, + ReLU when p.in_relu).  When a 16-channel block has landed in LDS, the workgroup rewrites it
-// once - join hi + lo, v * scale + shift (a multiply and an add, as avs_bn_apply), ReLU, split - behind one extra barrier,
-// and the nine taps read the finished values: the apply pass over the input (a read and a write of it in HBM) disappears.
-// The zero rows the padding taps read stay zero (the padding belongs to the finished activation), so the products, the
-// outputs and the statistics are those of avs_bn_apply followed by the plain form, bit for bit.
-// Which group a buffer row belongs to is answered in one of two ways.  Groups of at least 384 rows and cin <= 128
-// (p.xin_table; every group of the trunk's layers 1-2): a tile's 384 buffer rows touch at most two groups, whose (scale,
-// shift) rows are copied into a 2 x cin x 2-float LDS table once per tile; the rewrite then reads its values and its
-// table row together and has no division and no global load (xin_block_tab).  Smaller groups or wider inputs: a division
-// and four 16-byte loads from L2 per (row, run) pair (xin_block).  The arithmetic per value is the same.
 template <int ES, int BN, bool ACC64, bool SPATIAL, int ROWB, int EPI, bool PIPE, int WR = 2, bool FASTK = false,
           int SPLIT = 0, bool TAP9 = false, bool AP8 = false, bool XIN = false, bool GROUPW = false>
 __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64 && ES == 2) ? 4 : 3) : 2) void igemm_kernel(
@@ -158,12 +81,18 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
   static_assert(!PIPE || (ROWB == 64 && !ACC64), "the 3-buffer pipeline is built for the 64-byte-row variants");
   static_assert(!ACC64 || (ES == 4 && BN == 64), "fp64 slice accumulation: fp32 operands, narrow tile only");
   static_assert(ROWB == 64 || ROWB == 128, "row bytes");
+  // ROWB = bytes of reduction per LDS row and step: 128 (fewer barriers per MAC; 64 KB of LDS, 2 workgroups per
+  // CU) for the long reductions, 64 (32 KB, 3 workgroups per CU: more DMA in flight) for the short ones, whose
+  // cost is the latency of their few loads and their stores rather than the matrix work.
   constexpr int CE = 16 / ES;        // elements per 16-byte chunk
   constexpr int BKE = ROWB / ES;     // elements per LDS row (one reduction step)
   constexpr int CPRR = ROWB / 16;    // 16-byte slots per LDS row
   constexpr int RPP = 256 / CPRR;    // rows staged per pass of the 256 threads
   constexpr int SH = ROWB == 128 ? 1 : 2;  // rows sharing one 256-byte bank row = 1 << SH
   constexpr int KS = ROWB / 32;      // MFMA sub-steps per row (two chunks each)
+  // WR: rows of waves.  2 = the 128 x BN tile (2 x 2 waves of 64 x BN/2); 4 = a 256 x BN tile (4 x 1 waves of 64 x BN):
+  // twice the matrix work per barrier and 0.75 (BN = 128) instead of 1 fragment read per MFMA, for layers with many
+  // rows whose cost is the loop itself (the N = 64 layers run 4 MFMAs per wave between barriers at WR = 2).
   constexpr int WC = 4 / WR;         // columns of waves
   constexpr int WCOLS = BN / WC;     // output columns per wave
   constexpr int A_ROWS = 64 * WR;
@@ -201,11 +130,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
 
   __shared__ uint4 lds[LDS_SLOTS];
 
-  // XCD-aware, bijective block remap: blocks that share an XCD (orig % 8)
-  // take consecutive tiles, so neighbouring column tiles reuse A rows in L2.
-  const unsigned nwg = gridDim.x, orig = blockIdx.x;
-  const unsigned q = nwg >> 3, rr = nwg & 7, xcd = orig & 7;
-  const unsigned wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
+  const unsigned wg = avs_xcd_remap(gridDim.x, blockIdx.x);
   const int tn = wg % p.tiles_n;
   const int tm = wg / p.tiles_n;
   const int m0 = EPI == EPI_BNLOCAL ? tm * p.tile_rows : tm * A_ROWS;
@@ -224,7 +149,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
   const int c = t & (CPRR - 1);
   const int rb = t / CPRR;                          // 0..RPP-1
-  const int cq = c ^ ((rb >> SH) & (CPRR - 1));     // the k-chunk this thread fetches into slot c
+  const int cq = AVS_LDS_CHUNK(CPRR, SH, rb, c);    // the k-chunk this thread fetches into slot c
 
   // ---- per-thread row bases (rows rb + 32*i of the A tile, and of the B tile) ----
   const char* a_base[NA];
@@ -273,14 +198,23 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
   int kh = kk / p.KW;
   int kw = kk - kh * p.KW;
 
-  // ---- FASTK state: per-row tap masks and 32-bit buffer offsets (vector), the tap walk (scalar) ----
-  // Operands are fetched with buffer_load_dwordx4 ... lds: address = resource base (SGPRs) + per-lane offset (one
-  // VGPR, fixed for the whole reduction) + scalar offset (the tap walk / the k step).  A lane whose tap falls into
-  // the padding (or whose row does not exist) presents an offset beyond num_records and the hardware returns
-  // zeros, so staging costs no vector arithmetic per step beyond that select.  The A base is moved back by the
-  // padding so that every row's own offset is non-negative; the launcher guarantees a tile's rows and the tap walk
-  // stay inside the 2 GiB window.
-  constexpr unsigned BUF_OOB = 0x80000000u;
+  // FASTK: cin is a multiple of one reduction step (and there are at most 32 taps), so a step never straddles a tap:
+  // the tap walk (kh, kw, ci) is the same for every thread - kept in scalar registers and advanced by additions -
+  // a row's padding test is one bit of a per-row tap mask built once, and a DMA source is base + scalar offset.
+  // (Measured on the 3x3 layers: the general staging code issues ~180 vector + scalar instructions per 16 MFMAs and
+  // the loop ran at 45 % matrix-core occupancy for that reason alone - with no staging at all it reaches 1.5 PFLOP/s.)
+  // AP8 (AVS_F16X2 convolution + statistics, 1x1 on dense rows, 256-row tiles: conv1 of the ResNet bottlenecks in layers
+  // 1-2): the input is an AVS_F16P8 tensor (fp16 hi + 8-bit remainder, 48 bytes per 16 channels).  The LDS-DMA staging is
+  // the AVS_F16X2 one with other source offsets: of the four 16-byte slots of an LDS row, slot "hi 0-7" takes the block's
+  // first 16 bytes, slot "hi 8-15" its second, slot "lo 0-7" the 16 remainder bytes and slot "lo 8-15" nothing (an
+  // out-of-range lane), and a step advances the source by 48 instead of 64 bytes: 3 instead of 4 bytes per input value from
+  // HBM, the same LDS image for the hi fragments.  A lane reads its 8 remainder bytes with one ds_read_b64 and rebuilds the
+  // fp16 lo fragment in registers (5 VALU operations per value, behind the hi*hi MFMAs of the step).  (A first version
+  // fetched the A fragments straight into registers - a wave owns its 64 rows for all columns on these tiles, nothing is
+  // shared - with buffer_load_dwordx4 + dwordx2 per lane: 19 - 25 % SLOWER than the AVS_F16X2 path, 16-byte pieces of 32
+  // rows per instruction; removed.)
+  // ---- FASTK state: per-row tap masks and 32-bit buffer offsets (vector), the tap walk (scalar); the addressing and the
+  // pieces shared with igemm_h2_local224_kernel: igemm_params.h ----
   unsigned amask[FASTK ? NA : 1];
   unsigned aoff[FASTK ? NA : 1], boff[FASTK ? NB : 1];
   int f_tap = 0, f_ci0 = 0, f_kw = 0;
@@ -289,23 +223,16 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
   __amdgpu_buffer_rsrc_t a_rsrc, b_rsrc;
   if constexpr (FASTK) {
     const int taps = p.K / p.cin;
-    // uniform tile origin: the first image the tile touches (or its first row on the linear-row path)
-    long long a_origin;
-    int n_first = 0;
-    if (p.lin_stride >= 0) {
-      // study build, bit 6 (1x1 layers, 64-byte steps): the INPUT is read reduction-step major too, x[k / 32][M][32] - what
-      // a channel-blocked activation layout would give the A operand (whole cache lines per DMA instruction)
-      a_origin = AVS_DEBUG_BIT(p, 64) ? (long long)m0 * BKE : (long long)m0 * p.lin_stride;
-    } else {
-      n_first = m0 / p.HoWo;
-      a_origin = (long long)n_first * p.x_img_stride - (long long)p.ph * p.x_row_stride - (long long)p.pw * p.x_px_stride;
-    }
-    a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(x) + a_origin * (AP8 ? 3 : ES), 0, (int)BUF_OOB, 0x00020000);
+    // study build, bit 6 (1x1 layers, 64-byte steps): the INPUT is read reduction-step major too, x[k / 32][M][32] - what
+    // a channel-blocked activation layout would give the A operand (whole cache lines per DMA instruction)
+    int n_first;
+    const long long a_origin = avs_tap_origin(p, m0, AVS_DEBUG_BIT(p, 64) ? (long long)BKE : p.lin_stride, n_first);
+    a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(x) + a_origin * (AP8 ? 3 : ES), 0, (int)AVS_BUF_OOB, 0x00020000);
     b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(w) + (p.w_kstep ? (long long)n0 * 64 : (long long)n0 * p.ldb * ES), 0, (int)BUF_OOB, 0x00020000);
+        const_cast<char*>(w) + (p.w_kstep ? (long long)n0 * 64 : (long long)n0 * p.ldb * ES), 0, (int)AVS_BUF_OOB, 0x00020000);
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
-      unsigned mk = 0, off = BUF_OOB;
+      unsigned mk = 0, off = AVS_BUF_OOB;
       int m = m0 + rb + RPP * i;
       if constexpr (EPI == EPI_BNLOCAL) {
         if (rb + RPP * i >= p.tile_rows) m = p.M;
@@ -315,7 +242,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
           // AVS_F16P8 rows: slot "hi 0-7" <- bytes 0-15 of the 48-byte block, "lo 0-7" <- the remainder bytes (32-47),
           // "hi 8-15" <- bytes 16-31, "lo 8-15" <- nothing
           mk = ~0u;
-          off = cq == 3 ? BUF_OOB : (unsigned)((long long)(m - m0) * p.lin_stride * 3) + (cq == 0 ? 0u : cq == 1 ? 32u : 16u);
+          off = cq == 3 ? AVS_BUF_OOB : (unsigned)((long long)(m - m0) * p.lin_stride * 3) + (cq == 0 ? 0u : cq == 1 ? 32u : 16u);
         } else if (p.lin_stride >= 0) {
           mk = ~0u;
           off = AVS_DEBUG_BIT(p, 64) ? (unsigned)((m - m0) * ROWB) + cq * 16
@@ -330,8 +257,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
           } else {
             mk = ~0u;
           }
-          off = (unsigned)(((long long)(n - n_first) * p.x_img_stride + (long long)(hi0[i] + p.ph) * p.x_row_stride +
-                            (long long)(wi0[i] + p.pw) * p.x_px_stride) * ES) + cq * 16;
+          off = avs_tap_first<ES>(p, n - n_first, hi0[i], wi0[i]) + cq * 16;
         }
       }
       amask[i] = mk;
@@ -339,7 +265,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i)
-      boff[i] = b_base[i] == nullptr ? BUF_OOB
+      boff[i] = b_base[i] == nullptr ? AVS_BUF_OOB
                 : p.w_kstep        ? (unsigned)((rb + RPP * i) * 64) + (unsigned)(cq >> 2) * (unsigned)p.N * 64u + (cq & 3) * 16
                                    : (unsigned)((long long)(rb + RPP * i) * p.ldb * ES) + cq * 16;
   }
@@ -353,7 +279,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
           unsigned off = aoff[i];
-          if constexpr (SPATIAL) off = ((amask[i] >> f_tap) & 1u) ? off : BUF_OOB;
+          if constexpr (SPATIAL) off = ((amask[i] >> f_tap) & 1u) ? off : AVS_BUF_OOB;
           __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(abuf + 256 * i), 16,
                                                    (int)off, f_koff, 0, 0);
         }
@@ -364,19 +290,8 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
           __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rsrc, (__attribute__((address_space(3))) void*)(bbuf + 256 * i), 16,
                                                    (int)boff[i], f_kb, 0, 0);
       }
-      f_kb += p.w_kstep ? p.N * ROWB : BKE * ES;   // (ROWB / 64 pieces of N x 64 bytes per step)
-      // next step (scalar): the same tap's next channel block, or the next tap
-      f_ci0 += BKE;
-      f_koff += AP8 ? 48 : (AVS_DEBUG_BIT(p, 64) ? p.M * ROWB : BKE * ES);
-      if (f_ci0 == p.cin) {
-        f_ci0 = 0;
-        ++f_tap;
-        f_koff += (int)((p.x_px_stride - p.cin) * ES);
-        if (++f_kw == p.KW) {
-          f_kw = 0;
-          f_koff += (int)((p.x_row_stride - (long long)p.KW * p.x_px_stride) * ES);
-        }
-      }
+      // (weights: ROWB / 64 pieces of N x 64 bytes per step)
+      avs_tap_advance<ES>(p, f_tap, f_ci0, f_kw, f_koff, f_kb, BKE, AP8 ? 48 : (AVS_DEBUG_BIT(p, 64) ? p.M * ROWB : BKE * ES), p.w_kstep ? p.N * ROWB : BKE * ES);
       return;
     }
     const bool kval = kc < p.K;
@@ -438,8 +353,20 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         for (int e = 0; e < 16; ++e) acc64[i][j][e] = 0.0;
   }
 
+  // SPLIT: 0 = operands as stored; 1 = AVS_F32_SPLIT (fp32 operands split into bf16 hi + lo in the loop);
+  // 2 = AVS_F16X2 (operands ARE stored as fp16 hi + lo runs: the 16-byte chunks of a step alternate hi8 | lo8, so the
+  // fragments need no arithmetic at all - three v_mfma_f32_32x32x16_f16 per 16 reduction elements - and the epilogue
+  // splits each output once, where it is produced, instead of every consumer splitting it per tile and step)
   const int steps = (p.K + BKE - 1) / BKE;
   if constexpr (TAP9) {
+    // TAP9 (AVS_F16X2, 3x3 / stride 1 / pad 1 on a dense NHWC input, 256-row tiles): for output pixel (y, x) and tap (dy, dx)
+    // the input pixel is row m + (dy - 1) W + (dx - 1) of the SAME flat pixel array the outputs are rows of.  So a 16-channel
+    // block of the tile's pixels (+ W + 1 rows of halo on either side: 384 buffer rows) is fetched ONCE - two buffers, a
+    // block ahead - and the nine taps of the block are nine reduction steps that read their A fragments from it at shifted
+    // rows; a tap that leaves the frame reads a row of zeros (per-lane tap masks; this also covers tiles that straddle
+    // frames).  Only the weights of a (block, tap) are fetched per step (a ring of three).  L2 -> LDS traffic of the A
+    // operand / 9: for the 64-column layers, which sit at the L2 -> LDS intake ceiling (~21 B / clk / CU) with the matrix
+    // cores 37 % busy.  The reduction runs block-major / tap-minor: another (fixed) summation order than the tap-major walk.
     constexpr int T9_NA = T9_AROWS / RPP;   // DMA instructions per wave and A block (6)
     // TGEN (bias + ReLU: Inception-v3's 1x7 / 7x1 / 3x3 / 1x3 / 3x1 stride-1 "same" layers): any KH x KW with the filter's
     // reach ph W + pw <= 64 rows, the input possibly a channel slice of a wider tensor (pixel stride > cin).  The 3x3 forms
@@ -453,19 +380,18 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
     const int w1 = TGEN ? tph * p.W + tpw : p.W + 1;
     // buffer row a holds flat input row m0 - w1 + a; the buffer window starts at the first row fetched
     const long long mbase = m0 > w1 ? m0 - w1 : 0;
-    const __amdgpu_buffer_rsrc_t a9 = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(x) + mbase * pxs * ES, 0,
-                                                                         (int)BUF_OOB, 0x00020000);
-    const __amdgpu_buffer_rsrc_t b9 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(w) + (p.w_kstep ? (long long)n0 * 64 : (long long)n0 * p.ldb * ES), 0, (int)BUF_OOB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t a9 = avs_buffer_window(x + mbase * pxs * ES);
+    const __amdgpu_buffer_rsrc_t b9 =
+        avs_buffer_window(w + (p.w_kstep ? (long long)n0 * 64 : (long long)n0 * p.ldb * ES));
     unsigned aoff9[T9_NA], boff9[NB];
 #pragma unroll
     for (int i = 0; i < T9_NA; ++i) {
       const long long m = (long long)m0 - w1 + rb + RPP * i;
-      aoff9[i] = (m >= 0 && m < p.M) ? (unsigned)((m - mbase) * pxs * ES) + cq * 16 : BUF_OOB;
+      aoff9[i] = (m >= 0 && m < p.M) ? (unsigned)((m - mbase) * pxs * ES) + cq * 16 : AVS_BUF_OOB;
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i)
-      boff9[i] = (n0 + rb + RPP * i >= p.N || rb + RPP * i >= BN) ? BUF_OOB
+      boff9[i] = (n0 + rb + RPP * i >= p.N || rb + RPP * i >= BN) ? AVS_BUF_OOB
                  : p.w_kstep                                      ? (unsigned)((rb + RPP * i) * 64) + (cq & 3) * 16
                                                                   : (unsigned)((long long)(rb + RPP * i) * p.ldb * ES) + cq * 16;
     // bit tp of vm[mt]: tap tp of this lane's row of block mt lies inside its frame
@@ -522,7 +448,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         const int brow = nt * 32 + lr;
         // sub-step hl: AVS_F16X2 = the hi / lo chunk of this lane half's 8 elements; bf16 = its chunk of 16-element half hl
         const int chunk = SPLIT == 2 ? 2 * lh + hl : 2 * hl + lh;
-        fb9[nt][hl] = (unsigned)(brow * CPRR + (chunk ^ ((brow >> SH) & (CPRR - 1)))) * 16u;
+        fb9[nt][hl] = (unsigned)AVS_LDS_SLOT(CPRR, SH, brow, chunk) * 16u;
       }
     const int nblk = p.cin / BKE;   // 16-channel blocks; step s = (block s / 9, tap s % 9)
     auto stage_a = [&](int blk, int buf) {
@@ -547,6 +473,17 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         ++sb_blk;
       }
     };
+    // XIN (TAP9, AVS_F16X2 convolution + statistics): the input is a RAW activation with its BatchNorm affine given per group
+    // (p.in_scale / p.in_shift, + ReLU when p.in_relu).  When a 16-channel block has landed in LDS, the workgroup rewrites it
+    // once - join hi + lo, v * scale + shift (a multiply and an add, as avs_bn_apply), ReLU, split - behind one extra barrier,
+    // and the nine taps read the finished values: the apply pass over the input (a read and a write of it in HBM) disappears.
+    // The zero rows the padding taps read stay zero (the padding belongs to the finished activation), so the products, the
+    // outputs and the statistics are those of avs_bn_apply followed by the plain form, bit for bit.
+    // Which group a buffer row belongs to is answered in one of two ways.  Groups of at least 384 rows and cin <= 128
+    // (p.xin_table; every group of the trunk's layers 1-2): a tile's 384 buffer rows touch at most two groups, whose (scale,
+    // shift) rows are copied into a 2 x cin x 2-float LDS table once per tile; the rewrite then reads its values and its
+    // table row together and has no division and no global load (xin_block_tab).  Smaller groups or wider inputs: a division
+    // and four 16-byte loads from L2 per (row, run) pair (xin_block).  The arithmetic per value is the same.
     // XIN: block b's 384 buffer rows x 2 runs of 8 channels (hi chunk + lo chunk), three (row, run) pairs per thread; the
     // rows outside the input (zeros, never read by a tap inside a frame) are left alone
     auto xin_block = [&](int b) {
@@ -559,22 +496,13 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         if (m < 0 || m >= p.M) continue;
         const int g = m / p.rows_per_group;
         const long long ch = (long long)g * p.cin + b * BKE + run * 8;
-        uint4& hi = ab[a * CPRR + ((2 * run) ^ ((a >> SH) & (CPRR - 1)))];
-        uint4& lo = ab[a * CPRR + ((2 * run + 1) ^ ((a >> SH) & (CPRR - 1)))];
-        float v[8], sc[8], sf[8];
-        avs_f16x2_join8(hi, lo, v);
-        *reinterpret_cast<float4*>(&sc[0]) = *reinterpret_cast<const float4*>(p.in_scale + ch);
-        *reinterpret_cast<float4*>(&sc[4]) = *reinterpret_cast<const float4*>(p.in_scale + ch + 4);
-        *reinterpret_cast<float4*>(&sf[0]) = *reinterpret_cast<const float4*>(p.in_shift + ch);
-        *reinterpret_cast<float4*>(&sf[4]) = *reinterpret_cast<const float4*>(p.in_shift + ch + 4);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[j] + sf[j];
-        if (p.in_relu) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
-        }
+        uint4& hi = ab[AVS_LDS_SLOT(CPRR, SH, a, 2 * run)];
+        uint4& lo = ab[AVS_LDS_SLOT(CPRR, SH, a, 2 * run + 1)];
+        float sc[8], sf[8];
+        avs_load8(p.in_scale + ch, sc);
+        avs_load8(p.in_shift + ch, sf);
         uint4 h, l;
-        avs_f16x2_split8(v, h, l);
+        avs_xin_affine8(hi, lo, sc, sf, p.in_relu, h, l);
         hi = h;
         lo = l;
       }
@@ -596,26 +524,18 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
         const int a = (t >> 1) + 128 * i;
-        ha[i] = ab + (unsigned)(a * CPRR + ((2 * run) ^ ((a >> SH) & (CPRR - 1)))) * 16u;
+        ha[i] = ab + (unsigned)AVS_LDS_SLOT(CPRR, SH, a, 2 * run) * 16u;
       }
       // one pair: join, v * scale + shift, ReLU, split, back into its two chunks; tv = scale 0-3 | 4-7 | shift 0-3 | 4-7
       auto finish = [&](int i, const uint4& hi, const uint4& lo, const uint4 (&tv)[4]) {
         const int m = m0 - w1 + (t >> 1) + 128 * i;
         if (m < 0 || m >= p.M) return;
-        float v[8];
-        avs_f16x2_join8(hi, lo, v);
         const float4 s0 = __builtin_bit_cast(float4, tv[0]), s1 = __builtin_bit_cast(float4, tv[1]);
         const float4 f0 = __builtin_bit_cast(float4, tv[2]), f1 = __builtin_bit_cast(float4, tv[3]);
         const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
         const float sf[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[j] + sf[j];
-        if (p.in_relu) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
-        }
         uint4 h, l;
-        avs_f16x2_split8(v, h, l);
+        avs_xin_affine8(hi, lo, sc, sf, p.in_relu, h, l);
         // (the lo chunk's slot is the hi chunk's with bit 0 flipped, whatever the swizzle: 16 bytes beside it)
         *reinterpret_cast<uint4*>(reinterpret_cast<char*>(lds) + (ha[i] - lds_base)) = h;
         *reinterpret_cast<uint4*>(reinterpret_cast<char*>(lds) + ((ha[i] ^ 16u) - lds_base)) = l;
@@ -690,7 +610,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         const int a = ((vm[mt] >> tap) & 1u) ? abase + mt * 32 + sig : T9_AROWS;   // outside the frame: the zero row
-        aaddr[mt] = abuf + (unsigned)a * ROWB + (unsigned)((SPLIT == 2 ? 2 * lh : lh) ^ ((a >> SH) & (CPRR - 1))) * 16u;
+        aaddr[mt] = abuf + (unsigned)a * ROWB + (unsigned)AVS_LDS_CHUNK(CPRR, SH, a, SPLIT == 2 ? 2 * lh : lh) * 16u;
       }
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) fa[0][mt] = avs_lds_read_b128(aaddr[mt]);
@@ -756,6 +676,10 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
     }
     __syncthreads();   // the epilogue's tables and staging regions alias the operand buffers
   } else if constexpr (PIPE) {
+    // PIPE: three operand buffers, the DMA of step s+2 is issued in step s; fragment reads are inline-asm
+    // ds_read_b128 and the waits are hand-counted (s_waitcnt vmcnt(N) + raw s_barrier), because hipcc orders every
+    // LDS read it can see behind ALL outstanding LDS-DMA (vmcnt(0)), which caps a plain-HIP loop at one step of
+    // prefetch.  Order per step: wait for this step's DMA -> barrier -> issue step s+2 -> read fragments -> MFMA.
     constexpr int NDMA = NA + NB;  // DMA instructions one stage() issues per wave
     const unsigned lds_base = (unsigned)(unsigned long long)((__attribute__((address_space(3))) char*)lds);
     // per-lane fragment byte offsets inside a buffer (ks = 0; ks = 1 flips bit 1 of the chunk)
@@ -768,12 +692,12 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         const int row = wr * 64 + mt * 32 + lr;
-        fa_off[mt][ks] = (unsigned)(row * CPRR + (chunk ^ ((row >> SH) & (CPRR - 1)))) * 16u;
+        fa_off[mt][ks] = (unsigned)AVS_LDS_SLOT(CPRR, SH, row, chunk) * 16u;
       }
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const int row = wc * WCOLS + nt * 32 + lr;
-        fb_off[nt][ks] = (unsigned)((A_ROWS + row) * CPRR + (chunk ^ ((row >> SH) & (CPRR - 1)))) * 16u;
+        fb_off[nt][ks] = (unsigned)((A_ROWS + row) * CPRR + AVS_LDS_CHUNK(CPRR, SH, row, chunk)) * 16u;
       }
     }
     stage(0);
@@ -796,7 +720,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
             // sub-step 1 of an AVS_F16P8 row: this lane half's 8 remainder bytes (the slot "lo 0-7" holds all 16)
             if (ks == 1) {
               const int row = wr * 64 + mt * 32 + lr;
-              frem[mt] = avs_lds_read_b64(bbase + (unsigned)(row * CPRR + (1 ^ ((row >> SH) & (CPRR - 1)))) * 16u + 8u * lh);
+              frem[mt] = avs_lds_read_b64(bbase + (unsigned)AVS_LDS_SLOT(CPRR, SH, row, 1) * 16u + 8u * lh);
               continue;
             }
           }
@@ -945,12 +869,12 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
   #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
           const int row = wr * 64 + mt * 32 + lr;
-          fa[ks][mt] = abuf[row * CPRR + (chunk ^ ((row >> SH) & (CPRR - 1)))];
+          fa[ks][mt] = abuf[AVS_LDS_SLOT(CPRR, SH, row, chunk)];
         }
   #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
           const int row = wc * WCOLS + nt * 32 + lr;
-          fb[ks][nt] = bbuf[row * CPRR + (chunk ^ ((row >> SH) & (CPRR - 1)))];
+          fb[ks][nt] = bbuf[AVS_LDS_SLOT(CPRR, SH, row, chunk)];
         }
       }
       // 2. DMA of the next tile into the other buffer: every wave finished reading it before the barrier
@@ -1031,6 +955,30 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
   }
 
   // ---- epilogue ----
+  // EPI: the epilogue is what a tile of a short reduction costs, so its common forms are compiled separately:
+  //   EPI_PLAIN  alpha == 1, no bias, no activation, no statistics (ResNet convolutions, projections)
+  //   EPI_STATS  EPI_PLAIN + fused BatchNorm batch statistics: per-tile partial column sums in the tile's own slots
+  //              (no atomics), folded in tile order by bn_fold_kernel: deterministic
+  //   EPI_ANY    everything decided at run time (bias per column / row, ReLU, alpha)
+  //   EPI_BRELU  alpha == 1, bias per column, ReLU (the folded-BatchNorm convolutions of Inception-v3; Linear+ReLU)
+  //   EPI_BNLOCAL bf16, 256-row tiles only: the whole BatchNorm in the epilogue WITHOUT any traffic between workgroups.
+  //              A tile holds floor(256 / rows_per_group) WHOLE groups (tile pitch = that many rows, the rest of the
+  //              256 rows idle), so a group's statistics are sums over this tile's accumulators alone: per-wave masked
+  //              column sums -> LDS across the four row-waves -> scale/shift table -> normalise (+ residual, + ReLU)
+  //              -> store.  No atomics, no waiting, deterministic.  Taken when groups are at most 256 rows and fill
+  //              at least 3/4 of the tile (per-frame 14x14 and 7x7 maps: 196 = 77 %, 5 x 49 = 96 %).
+  // (A form in which tiles of larger groups exchanged statistics through float atomics and waited for each other inside
+  //  one launch was built in round 1 and removed: results were not reproducible run to run and it only won for groups of
+  //  two or three tiles, which the tile-local form covers.)
+  //   EPI_AFFINE AVS_F16X2, 1x1 convolutions: a folded BatchNorm affine GIVEN per group of rows (computed beforehand from
+  //              the input's Gram matrix, avs_bn_gram_affine_f16x2) + residual + ReLU: the one streaming pass of the
+  //              expanding 1x1 layers whose groups are too large for a tile.  256-row tiles; 128-row tiles (three
+  //              workgroups per CU) for wide outputs of reductions up to 128 channels.  Two instantiations: the general one
+  //              keeps the affines of the up to three groups a wave's 64 rows can lie in and picks one per value (two
+  //              compares, two selects per scale and shift); GROUPW, which the plan takes when rows_per_group is a multiple
+  //              of 64 (the trunk's 56 x 56 and 28 x 28 maps): a wave's rows start at a multiple of 64, so the wave lies in
+  //              ONE group - one (scale, shift) per column tile, no selects, and the residual's own affine (p.res_scale)
+  //              loaded once per tile instead of per run behind a 64-bit division.  The same fmaf per value: the same bits
   if constexpr (SPLIT == 2) {
     // AVS_F16X2 output.  Statistics (EPI_STATS / EPI_BNLOCAL) are taken in TWO rounds over the fp32 accumulators: column
     // sums -> the mean of the rows a tile holds of each group -> sums of squares ABOUT that mean, so nothing cancels
@@ -1057,7 +1005,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+            const int roff = avs_acc_row(mt * 32, e);
             s += (roff >= lo && roff < hi) ? acc[mt][nt][e] : 0.f;
           }
       }
@@ -1078,7 +1026,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+            const int roff = avs_acc_row(mt * 32, e);
             const float d = acc[mt][nt][e] - mean;
             s = (roff >= lo && roff < hi) ? fmaf(d, d, s) : s;
           }
@@ -1336,7 +1284,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
             if constexpr (GROUPW) {
               acc[mt][nt][e] = fmaf(acc[mt][nt][e], sc0[nt], sf0[nt]);
             } else {
-              const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+              const int roff = avs_acc_row(mt * 32, e);
               const bool in1 = roff >= bnd1, in2 = roff >= bnd2;
               const float sc = in2 ? sc2[nt] : (in1 ? sc1[nt] : sc0[nt]);
               const float sf = in2 ? sf2[nt] : (in1 ? sf1[nt] : sf0[nt]);
@@ -1349,12 +1297,8 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
     if constexpr (GROUPW) {
       if (p.res_scale) {
         const long long gq = col_ok ? wgrp * p.N + col8 : 0;   // (a lane without columns reads the first run: never used)
-        const float4 a0 = *reinterpret_cast<const float4*>(p.res_scale + gq);
-        const float4 a1 = *reinterpret_cast<const float4*>(p.res_scale + gq + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(p.res_shift + gq);
-        const float4 b1 = *reinterpret_cast<const float4*>(p.res_shift + gq + 4);
-        ras[0] = a0.x, ras[1] = a0.y, ras[2] = a0.z, ras[3] = a0.w, ras[4] = a1.x, ras[5] = a1.y, ras[6] = a1.z, ras[7] = a1.w;
-        rbs[0] = b0.x, rbs[1] = b0.y, rbs[2] = b0.z, rbs[3] = b0.w, rbs[4] = b1.x, rbs[5] = b1.y, rbs[6] = b1.z, rbs[7] = b1.w;
+        avs_load8(p.res_scale + gq, ras);
+        avs_load8(p.res_shift + gq, rbs);
       }
     }
 #pragma unroll
@@ -1363,7 +1307,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
       for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int e = 0; e < 16; ++e)
-          wreg[((e & 3) + 8 * (e >> 2) + 4 * lh) * H2_P + nt * 32 + lr] = acc[mt][nt][e];
+          wreg[(avs_acc_row(0, e) + 4 * lh) * H2_P + nt * 32 + lr] = acc[mt][nt][e];
       // half 1's residual rows: in flight while half 0 is processed (its accumulators have just left their registers)
       if (mt == 0 && NORM && p.residual) res_fetch(std::integral_constant<int, 1>{});
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1405,12 +1349,9 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
                 }
               } else if (p.res_scale) {   // the residual is a raw convolution output: its BatchNorm rides in the add
                 const long long gq = (row / p.rows_per_group) * p.N + col8;
-                const float4 a0 = *reinterpret_cast<const float4*>(p.res_scale + gq);
-                const float4 a1 = *reinterpret_cast<const float4*>(p.res_scale + gq + 4);
-                const float4 b0 = *reinterpret_cast<const float4*>(p.res_shift + gq);
-                const float4 b1 = *reinterpret_cast<const float4*>(p.res_shift + gq + 4);
-                const float as[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                const float bs[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+                float as[8], bs[8];
+                avs_load8(p.res_scale + gq, as);
+                avs_load8(p.res_shift + gq, bs);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) rv[j] = fmaf(rv[j], as[j], bs[j]);
               }
@@ -1442,7 +1383,6 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
       __builtin_amdgcn_wave_barrier();
     }
   } else {
-  // Register e of a 32x32 tile is row (e&3) + 8*(e>>2) + 4*lh, column lr.
   constexpr int E_CPRW = BN / 8;           // 16-byte chunks per bf16 tile row
   constexpr int E_RSTEP = 256 / E_CPRW;    // tile rows covered by one pass of the 256 threads
   constexpr int E_NIT = A_ROWS / E_RSTEP;
@@ -1484,7 +1424,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
               for (int e = 0; e < 16; ++e) {
-                const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);  // row - r_first - 4*lh
+                const int roff = avs_acc_row(mt * 32, e);  // row - r_first - 4*lh
                 const float v = (roff >= lo && roff < hi) ? acc[mt][nt][e] : 0.f;
                 s1 += v;
                 s2 = fmaf(v, v, s2);
@@ -1593,7 +1533,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
               for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                  const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+                  const int roff = avs_acc_row(mt * 32, e);
                   const float v = (roff >= lo && roff < hi) ? acc[mt][nt][e] : 0.f;
                   s1 += v;
                   s2 = fmaf(v, v, s2);
@@ -1649,11 +1589,10 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
           for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int e = 0; e < 16; e += 2) {   // rows r, r + 1 of one column: one conversion, ReLU on the packed pair
-              const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+              const int roff = avs_acc_row(mt * 32, e);
               unsigned pk = avs_pack_bf16x2(fmaf(acc[mt][nt][e], sc, sf), fmaf(acc[mt][nt][e + 1], sc, sf));
               if (relu_now) pk = avs_relu_bf16x2(pk);
-              *reinterpret_cast<unsigned short*>(cbase + roff * CT_PITCH + nt * 64) = (unsigned short)pk;
-              *reinterpret_cast<unsigned short*>(cbase + (roff + 1) * CT_PITCH + nt * 64) = (unsigned short)(pk >> 16);
+              avs_ct_store2<CT_PITCH>(cbase, roff, nt, pk);
             }
         }
       } else {
@@ -1673,17 +1612,16 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
               float v2[2];
 #pragma unroll
               for (int h = 0; h < 2; ++h) {
-                const int roff = mt * 32 + ((e + h) & 3) + 8 * ((e + h) >> 2);
+                const int roff = avs_acc_row(mt * 32, e + h);
                 const bool g1 = roff >= b1, g2 = roff >= b2;
                 const float sc = g2 ? sc2 : (g1 ? sc1 : sc0);
                 const float sf = g2 ? sf2 : (g1 ? sf1 : sf0);
                 v2[h] = fmaf(acc[mt][nt][e + h], sc, sf);
               }
-              const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+              const int roff = avs_acc_row(mt * 32, e);
               unsigned pk = avs_pack_bf16x2(v2[0], v2[1]);
               if (relu_now) pk = avs_relu_bf16x2(pk);
-              *reinterpret_cast<unsigned short*>(cbase + roff * CT_PITCH + nt * 64) = (unsigned short)pk;
-              *reinterpret_cast<unsigned short*>(cbase + (roff + 1) * CT_PITCH + nt * 64) = (unsigned short)(pk >> 16);
+              avs_ct_store2<CT_PITCH>(cbase, roff, nt, pk);
             }
         }
       }
@@ -1744,7 +1682,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
           }
 #pragma unroll
           for (int e = 0; e < 16; e += 2) {   // rows r, r + 1 of one column: one conversion, ReLU on the packed pair
-            const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+            const int roff = avs_acc_row(mt * 32, e);
             float v2[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -1764,8 +1702,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
               if (p.act == AVS_ACT_RELU) pk = avs_relu_bf16x2(pk);
             }
             if constexpr (EPI == EPI_BRELU) pk = avs_relu_bf16x2(pk);
-            *reinterpret_cast<unsigned short*>(cbase + roff * CT_PITCH + nt * 64) = (unsigned short)pk;
-            *reinterpret_cast<unsigned short*>(cbase + (roff + 1) * CT_PITCH + nt * 64) = (unsigned short)(pk >> 16);
+            avs_ct_store2<CT_PITCH>(cbase, roff, nt, pk);
           }
         }
     }
@@ -1810,7 +1747,7 @@ __global__ __launch_bounds__(256, (ROWB == 64 && !ACC64 && WR == 2) ? ((BN == 64
         if constexpr (EPI == EPI_BRELU) bcol = bias[col];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int row = m0 + wr * 64 + mt * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+          const int row = avs_acc_row(m0 + wr * 64 + mt * 32, e) + 4 * lh;
           if (row >= p.M) continue;
           float v;
           if constexpr (ACC64)

@@ -1,5 +1,6 @@
-// Shared by the contraction kernels of libavsum_hip.so (igemm.hip, local224.hip): the launch parameters, the epilogue
-// forms and the inline-asm helpers of the hand-counted pipelines.
+// Shared by the contraction kernels of libavsum_hip.so (igemm.hip, local224.hip; convbn.hip takes the block remap, the LDS
+// slot map and AVS_GLDS16): the launch parameters, the epilogue forms, the inline-asm helpers of the hand-counted pipelines
+// and the pieces of staging and epilogue text these kernels have in common.
 #pragma once
 #include "avs_internal.h"
 
@@ -109,6 +110,98 @@ __device__ __forceinline__ uint4 avs_lds_read_b128(unsigned byte_addr) {
   uint4 v;
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(byte_addr));
   return v;
+}
+
+// ---- pieces the contraction kernels share (igemm.hip, local224.hip, convbn.hip): each stated once, here ----
+// 16 bytes from a per-lane global address straight into LDS (wave-linear destination)
+#define AVS_GLDS16(src, dst)                                                                        \
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),            \
+                                   (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
+
+// XCD-aware, bijective block remap: blocks that share an XCD (orig % 8) take consecutive tiles, so neighbouring column
+// tiles reuse A rows in L2.  nwg = gridDim.x, orig = blockIdx.x
+__device__ __forceinline__ unsigned avs_xcd_remap(unsigned nwg, unsigned orig) {
+  const unsigned q = nwg >> 3, rr = nwg & 7, xcd = orig & 7;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
+}
+
+// The LDS image of an operand tile: a row is CPRR 16-byte slots, chunk q of row r lives in slot q ^ (r >> SH) mod CPRR (1 << SH
+// rows share a 256-byte bank row).  Its own inverse: the chunk a thread FETCHES into slot c of row r is AVS_LDS_CHUNK(r, c).
+// (Macros: as functions the expressions reach the optimiser in another order, which added instructions to the hot kernels.)
+#define AVS_LDS_CHUNK(CPRR, SH, row, chunk) ((chunk) ^ (((row) >> SH) & (CPRR - 1)))
+#define AVS_LDS_SLOT(CPRR, SH, row, chunk) ((row) * CPRR + AVS_LDS_CHUNK(CPRR, SH, row, chunk))
+
+// Register e of a 32x32 accumulator tile is row (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5), column lane & 31.  The row
+// counted from `base` (a block's first row); the sum stays in this order, which is the order the kernels were written in
+__device__ __forceinline__ constexpr int avs_acc_row(int base, int e) { return base + (e & 3) + 8 * (e >> 2); }
+
+// eight consecutive floats as two 16-byte loads
+__device__ __forceinline__ void avs_load8(const float* src, float (&v)[8]) {
+  const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
+  v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+}
+// ---- the buffer-load staging of the scalar tap walk (igemm_kernel's FASTK branch, igemm_h2_local224_kernel) ----
+// Operands are fetched with buffer_load_dwordx4 ... lds: address = resource base (SGPRs) + per-lane offset (one
+// VGPR, fixed for the whole reduction) + scalar offset (the tap walk / the k step).  A lane whose tap falls into
+// the padding (or whose row does not exist) presents an offset beyond num_records and the hardware returns
+// zeros, so staging costs no vector arithmetic per step beyond that select.  The A base is moved back by the
+// padding so that every row's own offset is non-negative; the launcher guarantees a tile's rows and the tap walk
+// stay inside the 2 GiB window.
+constexpr unsigned AVS_BUF_OOB = 0x80000000u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t avs_buffer_window(const char* base) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, (int)AVS_BUF_OOB, 0x00020000);
+}
+// uniform tile origin, in elements: the first image the tile touches (n_first), or its first row (lin_row elements apart)
+__device__ __forceinline__ long long avs_tap_origin(const IgemmParams& p, int m0, long long lin_row, int& n_first) {
+  n_first = 0;
+  if (p.lin_stride >= 0) return (long long)m0 * lin_row;
+  n_first = m0 / p.HoWo;
+  return (long long)n_first * p.x_img_stride - (long long)p.ph * p.x_row_stride - (long long)p.pw * p.x_px_stride;
+}
+// a row's 32-bit offset: its first tap relative to the tile origin, n_rel = the row's image minus the tile's first
+template <int ES>
+__device__ __forceinline__ unsigned avs_tap_first(const IgemmParams& p, int n_rel, int hi0, int wi0) {
+  return (unsigned)(((long long)n_rel * p.x_img_stride + (long long)(hi0 + p.ph) * p.x_row_stride +
+                     (long long)(wi0 + p.pw) * p.x_px_stride) * ES);
+}
+// The tap walk (kh, kw, ci) is the same for every thread: kept in scalar registers and advanced by additions.  Next step: the
+// same tap's next channel block (step_elems channels = a_step bytes further), or the next tap; b_step = bytes between a weight
+// row's steps.  f_koff: bytes, the current tap + channel block relative to a row's first tap; f_kb: bytes, the current k step
+// inside a B row.  (Five ints by reference: as a struct the walk moved instructions in 236 of igemm_kernel's instantiations.)
+template <int ES>
+__device__ __forceinline__ void avs_tap_advance(const IgemmParams& p, int& f_tap, int& f_ci0, int& f_kw, int& f_koff,
+                                                int& f_kb, int step_elems, int a_step, int b_step) {
+  f_kb += b_step;
+  f_ci0 += step_elems;
+  f_koff += a_step;
+  if (f_ci0 == p.cin) {
+    f_ci0 = 0;
+    ++f_tap;
+    f_koff += (int)((p.x_px_stride - p.cin) * ES);
+    if (++f_kw == p.KW) {
+      f_kw = 0;
+      f_koff += (int)((p.x_row_stride - (long long)p.KW * p.x_px_stride) * ES);
+    }
+  }
+}
+// XIN, a run of 8 channels of the raw activation: join hi + lo, v * scale + shift (a multiply and an add, as avs_bn_apply), ReLU, split
+__device__ __forceinline__ void avs_xin_affine8(const uint4& hi, const uint4& lo, const float (&sc)[8], const float (&sf)[8],
+                                                int relu, uint4& h, uint4& l) {
+  float v[8];
+  avs_f16x2_join8(hi, lo, v);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[j] + sf[j];
+  if (relu) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
+  }
+  avs_f16x2_split8(v, h, l);
+}
+// rows roff, roff + 1 of a column of the packed-bf16 staging tile (pitch PITCH bytes; cbase: the lane's row 0, tile 0): two 2-byte stores
+template <int PITCH>
+__device__ __forceinline__ void avs_ct_store2(char* cbase, int roff, int nt, unsigned pk) {
+  *reinterpret_cast<unsigned short*>(cbase + roff * PITCH + nt * 64) = (unsigned short)pk;
+  *reinterpret_cast<unsigned short*>(cbase + (roff + 1) * PITCH + nt * 64) = (unsigned short)(pk >> 16);
 }
 
 // What igemm_plan() chooses for one call - which kernel (the template arguments of igemm_kernel, or the 224-row tile of

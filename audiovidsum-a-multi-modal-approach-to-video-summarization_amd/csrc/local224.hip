@@ -37,7 +37,6 @@ constexpr int L_CPRR = 4;                   // 16-byte slots per 64-byte LDS row
 constexpr int L_STEP = 16;                  // reduction elements (slots) per step
 constexpr int L_BUF = (L_ROWS + L_BN) * L_CPRR;   // uint4 slots per operand buffer
 constexpr int L_P = 32 + 8;                 // words per staged output row
-constexpr unsigned L_OOB = 0x80000000u;
 
 template <int OFF>
 __device__ __forceinline__ uint4 lds_read_b128_at(unsigned byte_addr) {
@@ -127,10 +126,8 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
   static_assert(SHAPE == 32 || SHAPE == 16, "SHAPE: 32 (v_mfma_f32_32x32x16_f16) or 16 (v_mfma_f32_16x16x32_f16)");
   __shared__ uint4 lds[3 * L_BUF];
 
-  // XCD-aware, bijective block remap (as igemm_kernel): blocks that share an XCD take consecutive tiles
   const unsigned nwg = gridDim.x, orig = blockIdx.x;
-  const unsigned q = nwg >> 3, rr = nwg & 7, xcd = orig & 7;
-  const unsigned wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
+  const unsigned wg = avs_xcd_remap(nwg, orig);   // (as igemm_kernel)
   int tn = wg % p.tiles_n;
   int tm = wg / p.tiles_n;
   if (p.packed) {
@@ -187,30 +184,21 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
   const bool extra = wave < 2;                      // this wave stages rows 192 .. 223 too
   const int c = t & (L_CPRR - 1);
   const int rb = t >> 2;                            // 0 .. 63
-  const int cq = c ^ ((rb >> 2) & (L_CPRR - 1));    // the k-chunk this thread fetches into slot c
+  const int cq = AVS_LDS_CHUNK(L_CPRR, 2, rb, c);   // the k-chunk this thread fetches into slot c
 
-  // ---- staging state: per-row tap masks and 32-bit buffer offsets (vector), the tap walk (scalar) ----
+  // ---- staging state: per-row tap masks and 32-bit buffer offsets (vector), the tap walk (scalar): igemm_params.h ----
   unsigned amask[4], aoff[4], boff[2];
-  int f_tap = 0, f_ci0 = 0, f_kw = 0;
-  int f_koff = 0;   // bytes: the current tap + channel block relative to a row's first tap
-  int f_kb = 0;     // bytes: the current k step inside a B row
+  int f_tap = 0, f_ci0 = 0, f_kw = 0, f_koff = 0, f_kb = 0;
   __amdgpu_buffer_rsrc_t a_rsrc, b_rsrc;
   {
     const int taps = p.K / p.cin;
-    long long a_origin;
-    int n_first = 0;
-    if (p.lin_stride >= 0) {
-      a_origin = (long long)m0 * p.lin_stride;
-    } else {
-      n_first = m0 / p.HoWo;
-      a_origin = (long long)n_first * p.x_img_stride - (long long)p.ph * p.x_row_stride - (long long)p.pw * p.x_px_stride;
-    }
-    a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(x) + a_origin * 4, 0, (int)L_OOB, 0x00020000);
-    b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(w) + (p.w_kstep ? (long long)n0 * 64 : (long long)n0 * p.ldb * 4), 0, (int)L_OOB, 0x00020000);
+    int n_first;
+    const long long a_origin = avs_tap_origin(p, m0, p.lin_stride, n_first);
+    a_rsrc = avs_buffer_window(x + a_origin * 4);
+    b_rsrc = avs_buffer_window(w + (p.w_kstep ? (long long)n0 * 64 : (long long)n0 * p.ldb * 4));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      unsigned mk = 0, off = L_OOB;
+      unsigned mk = 0, off = AVS_BUF_OOB;
       const int r = rb + 64 * i;
       if (r < used) {
         const int m = m0 + r;
@@ -231,8 +219,7 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
           } else {
             mk = ~0u;
           }
-          off = (unsigned)(((long long)(n - n_first) * p.x_img_stride + (long long)(hi0 + p.ph) * p.x_row_stride +
-                            (long long)(wi0 + p.pw) * p.x_px_stride) * 4) + cq * 16;
+          off = avs_tap_first<4>(p, n - n_first, hi0, wi0) + cq * 16;
         }
       }
       amask[i] = mk;
@@ -250,13 +237,13 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       unsigned off = aoff[i];
-      if constexpr (SPATIAL) off = ((amask[i] >> f_tap) & 1u) ? off : L_OOB;
+      if constexpr (SPATIAL) off = ((amask[i] >> f_tap) & 1u) ? off : AVS_BUF_OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(abuf + 256 * i), 16,
                                                (int)off, f_koff, 0, 0);
     }
     if (extra) {
       unsigned off = aoff[3];
-      if constexpr (SPATIAL) off = ((amask[3] >> f_tap) & 1u) ? off : L_OOB;
+      if constexpr (SPATIAL) off = ((amask[3] >> f_tap) & 1u) ? off : AVS_BUF_OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(abuf + 256 * 3), 16,
                                                (int)off, f_koff, 0, 0);
     }
@@ -264,19 +251,7 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
     for (int i = 0; i < 2; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rsrc, (__attribute__((address_space(3))) void*)(bbuf + 256 * i), 16,
                                                (int)boff[i], f_kb, 0, 0);
-    f_kb += p.w_kstep ? p.N * 64 : L_STEP * 4;
-    // next step (scalar): the same tap's next channel block, or the next tap
-    f_ci0 += L_STEP;
-    f_koff += L_STEP * 4;
-    if (f_ci0 == p.cin) {
-      f_ci0 = 0;
-      ++f_tap;
-      f_koff += (int)((p.x_px_stride - p.cin) * 4);
-      if (++f_kw == p.KW) {
-        f_kw = 0;
-        f_koff += (int)((p.x_row_stride - (long long)p.KW * p.x_px_stride) * 4);
-      }
-    }
+    avs_tap_advance<4>(p, f_tap, f_ci0, f_kw, f_koff, f_kb, L_STEP, L_STEP * 4, p.w_kstep ? p.N * 64 : L_STEP * 4);
   };
 
   const int lr = lane & 31, lh = lane >> 5;
@@ -308,13 +283,11 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
   unsigned fa16_even, fa16_odd, fb16_p, fb16_q;
   {
     const int hk = 2 * (lg & 1);
-    const int sw = (rho >> 2) & (L_CPRR - 1);
-    fa16_even = (unsigned)(rho * L_CPRR + ((hk + (lg >> 1)) ^ sw)) * 16u;
-    fa16_odd = (unsigned)(rho * L_CPRR + ((hk + 1 - (lg >> 1)) ^ sw)) * 16u;
+    fa16_even = (unsigned)AVS_LDS_SLOT(L_CPRR, 2, rho, hk + (lg >> 1)) * 16u;
+    fa16_odd = (unsigned)AVS_LDS_SLOT(L_CPRR, 2, rho, hk + 1 - (lg >> 1)) * 16u;
     const int brow = wave * 32 + li;
-    const int swb = (brow >> 2) & (L_CPRR - 1);
-    fb16_p = (unsigned)((L_ROWS + brow) * L_CPRR + (hk ^ swb)) * 16u;
-    fb16_q = (unsigned)((L_ROWS + brow) * L_CPRR + ((hk + 1) ^ swb)) * 16u;
+    fb16_p = (unsigned)((L_ROWS + brow) * L_CPRR + AVS_LDS_CHUNK(L_CPRR, 2, brow, hk)) * 16u;
+    fb16_q = (unsigned)((L_ROWS + brow) * L_CPRR + AVS_LDS_CHUNK(L_CPRR, 2, brow, hk + 1)) * 16u;
   }
 
   // per-lane fragment byte offsets inside a buffer: a row's chunks alternate hi8 | lo8; this lane half feeds elements
@@ -325,9 +298,9 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
 #pragma unroll
   for (int hl = 0; hl < 2; ++hl) {
     const int chunk = 2 * lh + hl;
-    fa_off[hl] = (unsigned)(lr * L_CPRR + (chunk ^ ((lr >> 2) & (L_CPRR - 1)))) * 16u;
+    fa_off[hl] = (unsigned)AVS_LDS_SLOT(L_CPRR, 2, lr, chunk) * 16u;
     const int brow = wave * 32 + lr;
-    fb_off[hl] = (unsigned)((L_ROWS + brow) * L_CPRR + (chunk ^ ((brow >> 2) & (L_CPRR - 1)))) * 16u;
+    fb_off[hl] = (unsigned)((L_ROWS + brow) * L_CPRR + AVS_LDS_CHUNK(L_CPRR, 2, brow, chunk)) * 16u;
   }
 
   // The residual rows of the first three blocks are fetched BEFORE the reduction (48 registers through the main loop),
@@ -523,7 +496,7 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
   }
 
   // ---- epilogue: the group's BatchNorm from this wave's own registers, then 32 rows at a time through LDS ----
-  // A lane holds column lr of its wave's 32, rows (e & 3) + 8 * (e >> 2) + 4 * lh of every block; rows >= used are
+  // A lane holds column lr of its wave's 32, rows avs_acc_row(0, e) + 4 * lh of every block; rows >= used are
   // exact zeros (their operand rows were never fetched).
   if (p.residual) {
     if constexpr (SHAPE == 16) res_fetch(std::integral_constant<int, 2>{});
@@ -610,7 +583,7 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
     for (int mt = 0; mt < L_MT; ++mt)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+        const int roff = avs_acc_row(mt * 32, e);
         if (mt < 3 || (mt == 3 && e < 8)) {
           const float d = acc[mt][e] - mean;
           s2 = roff < lim ? fmaf(d, d, s2) : s2;
@@ -635,7 +608,7 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
     for (int mt = 0; mt < L_MT; ++mt)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int roff = mt * 32 + (e & 3) + 8 * (e >> 2);
+        const int roff = avs_acc_row(mt * 32, e);
         const float d = acc[mt][e] - mean;
         s2 = roff < lim ? fmaf(d, d, s2) : s2;
       }
@@ -801,7 +774,7 @@ __global__ __launch_bounds__(256, 2) void igemm_h2_local224_kernel(IgemmParams p
     constexpr int mt = decltype(blk)::value;
     if constexpr (SHAPE == 32) {
 #pragma unroll
-      for (int e = 0; e < 16; ++e) wreg[((e & 3) + 8 * (e >> 2) + 4 * lh) * L_P + lr] = acc[mt][e];
+      for (int e = 0; e < 16; ++e) wreg[(avs_acc_row(0, e) + 4 * lh) * L_P + lr] = acc[mt][e];
     } else {
       // two 16-row blocks make the 32 staged rows; lanes li and 16 + li of a store share a bank (two-way: free for stores)
 #pragma unroll
