@@ -17,10 +17,14 @@ class BaseDataset(torch.utils.data.Dataset):
         return len(self.video_ids)
 
     def _features(self, vid):
-        return {
+        features = {
             "visual": torch.from_numpy(np.load(os.path.join(self.feature_dir, vid, "visual.npy"))),
             "audio": torch.from_numpy(np.load(os.path.join(self.feature_dir, vid, "audio.npy"))),
         }
+        shots = os.path.join(self.feature_dir, vid, "shots.npy")     # (only where save_features was given the shots)
+        if os.path.exists(shots):
+            features["shots"] = torch.from_numpy(np.load(shots))
+        return features
 
     def __getitem__(self, idx):
         vid = self.video_ids[idx]
@@ -49,8 +53,10 @@ class SumMeDataset(BaseDataset):
         return loadmat(mat_path)["gt_score"].squeeze()
 
 
-def save_features(output_dir, video_name, visual, audio):
-    """The writer side of the format (scripts/preprocess.py:66-81): validates 4096/296 and saves float32."""
+def save_features(output_dir, video_name, visual, audio, shots=None):
+    """The writer side of the format (scripts/preprocess.py:66-81): validates 4096/296 and saves float32.  ``shots``:
+    the [(start, end)] frame bounds of the rows, one per row; given, they are saved beside as shots.npy (int64 [S, 2]),
+    what collate_videos(targets="shots") needs."""
     if visual.shape[1] != 4096:
         raise ValueError(f"Invalid visual shape: {visual.shape}")
     if audio.shape[1] != 296:
@@ -59,3 +65,8 @@ def save_features(output_dir, video_name, visual, audio):
     os.makedirs(d, exist_ok=True)
     np.save(os.path.join(d, "visual.npy"), visual.astype(np.float32))
     np.save(os.path.join(d, "audio.npy"), audio.astype(np.float32))
+    if shots is not None:
+        table = np.asarray(shots, dtype=np.int64).reshape(-1, 2)
+        if table.shape[0] != visual.shape[0]:
+            raise ValueError(f"Invalid shot table: {table.shape[0]} shots for {visual.shape[0]} rows")
+        np.save(os.path.join(d, "shots.npy"), table)

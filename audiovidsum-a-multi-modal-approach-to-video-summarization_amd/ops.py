@@ -13,7 +13,7 @@ from ._abi import (ACT_NONE, ACT_RELU, AVS_BF16, AVS_F16X2, AVS_F32, AVS_F32_SPL
                    lib)
 from .ragged import (ATTN_BWD_TILE, ATTN_FWD_TILE, AttnTable, EVAL_CHUNK, EVAL_COLS, EVAL_MAX_T, EVAL_TILE, FUSION_MAX_N, FUSION_MID_L, FUSION_SMALL_L,  # noqa: F401
                      KTS_MAX_SAMPLES, SHOT_INTERVAL, SHOT_MAX_FRAMES, SHOT_MICRO_BATCH, SUMMARY_MAX_CAPACITY, SUMMARY_MAX_ROWS,
-                     EvalTables, FusionTables, KtsTables, RaggedOffsets, SeqTable, ShotTables, StageOneTables,
+                     EvalTables, FusionTables, KtsTables, RaggedOffsets, RankTables, SeqTable, ShotTables, StageOneTables,
                      SummaryTables)
 
 __all__ = [
@@ -23,6 +23,7 @@ __all__ = [
     "gather_scale", "FusionTables", "fusion_batch", "EvalTables", "eval_counts", "segment_mean_mask", "dtype_code", "f16x2_pack", "f16x2_unpack", "bn_gram_affine_h2", "conv2d_affine",
     "SeqTable", "seq_shift_rows", "seq_mse",
     "AttnTable",
+    "RankTables",
     "ShotTables", "hsv_frame_diff_batch", "shot_cuts_batch", "shot_tables", "gather_rows",
     "SummaryTables", "shot_value_sums", "knapsack_batch", "mask_overlap_counts",
     "StageOneTables", "resize_gather", "segment_mean_perm",

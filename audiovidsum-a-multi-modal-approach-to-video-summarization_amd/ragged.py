@@ -1,5 +1,6 @@
 """Host plans of the ragged-batch layers: row offsets validated on the host and uploaded once (RaggedOffsets and the
-seven tables built on it - EvalTables, SeqTable, AttnTable, ShotTables, StageOneTables, SummaryTables, KtsTables) and the
+eight tables built on it - EvalTables, SeqTable, AttnTable, ShotTables, StageOneTables, SummaryTables, KtsTables,
+RankTables) and the
 pair tables of the batched fusion (FusionTables).
 Pure host code on numpy and torch: nothing here touches the kernel library, so the plans can be built and checked with
 ``device="cpu"`` where there is no GPU.  ops.py re-exports every name and holds the launch wrappers that take them."""
@@ -8,6 +9,7 @@ import torch
 
 from ._attn_abi import load_header as _load_attn_header   # (the header's reader only: the library is not loaded here)
 from ._header import load as _load_header
+from ._loss_abi import load_header as _load_loss_header   # (again the reader only)
 from .features.kts import KTS_MAX_SAMPLES, kts_penalties   # (pure numpy: the limit and the penalty of the definitions)
 
 # The sizes the tables below share with the kernels that read them are the header's (include/avsum_hip.h, where each is
@@ -44,6 +46,12 @@ ATTN_FWD_TILE = _HA["AVSA_FWD_TILE"]         # 128: queries of a forward workgro
 ATTN_BWD_TILE = _HA["AVSA_BWD_TILE"]         # 32: keys of a dK/dV workgroup = queries of a dQ workgroup
 _ATTN_TILE_COLS = _HA["AVSA_TILE_COLS"]      # 2: int32 per row of a tile table
 _ATTN_MAX_ROWS = _HA["AVSA_MAX_ROWS"]        # 2^31 - 1: the last offset at most
+
+# include/avsum_loss.h: the tile of the pairwise ranking loss and its limits
+_HL = _load_loss_header().constants
+RANK_TILE = _HL["AVSL_TILE"]                 # 256: rows of a video per workgroup of the pair kernel
+RANK_MAX_T = _HL["AVSL_MAX_T"]               # 32768: rows of one video (pair counts: < 2^30 per row, < 2^31 per video)
+_RANK_TILE_COLS = _HL["AVSL_TILE_COLS"]      # 2: int32 per row of the tile table
 
 
 def exclusive_offsets(lengths):
@@ -409,6 +417,27 @@ class KtsTables(RaggedOffsets):
         cut video ``v`` into: b_0 = 0, b_j = cp[j - 1] * stride, the last end N_v."""
         b = [0] + [int(c) * self.stride for c in change_points] + [int(self.lengths[v])]
         return list(zip(b[:-1], b[1:]))
+
+
+class RankTables(RaggedOffsets):
+    """The host plan of one batch layout for the pairwise ranking loss (loss.rank_loss), built once from the host row
+    offsets [V + 1] of the videos in the concatenated scores (video v is rows offsets[v] .. offsets[v + 1]).
+
+    Host side (numpy): ``offsets``, ``lengths`` (int64), ``nseq``, ``rows`` (= offsets[-1]), ``max_t``, ``tiles`` int32
+    [ntiles, 2] = (video, row tile of 256 rows) - every video's tiles 0 .. ceil(T_v / 256) - 1, video after video -
+    ``ntiles``.  Device side: ``offsets_t`` int64 [V + 1], ``tiles_t``, uploaded once.  ``device="cpu"`` keeps everything
+    on the host (the builder can be checked without a GPU or the library).  Refused, each with a ValueError: an empty
+    batch, offsets that do not start at 0 or do not increase strictly, a video longer than 32768 rows (its pair counts
+    stay below 2^30 per row and below 2^31 summed over a video), 2^31 rows or more.  A video of one row is allowed: it
+    has no pair, its loss and gradient are 0."""
+
+    def __init__(self, offsets_host, rows=None, device=None):
+        super().__init__(offsets_host, "RankTables", device=device, max_length=RANK_MAX_T, rows=rows)
+        self.nseq, self.rows, self.max_t = self.count, self.total, self.max_len
+        self.tiles = np.stack(segment_tiles(-(-self.lengths // RANK_TILE)), 1).astype(np.int32).reshape(
+            -1, _RANK_TILE_COLS)
+        self.ntiles = self.tiles.shape[0]
+        self.tiles_t, = _upload(self.device, self.tiles)
 
 
 class FusionTables:
