@@ -18,6 +18,7 @@ import torch.nn as nn
 from .. import ops
 from ..audio import MelPlan
 from ..ingest import Nv12Frames, nv12_resize_gather, nv12_to_bgr
+from ..yuv import YuvFrames, yuv_resize_gather, yuv_to_bgr
 from ..cnn import InceptionV3Runner, Inception3, ResNet50Runner, RESNET_MEAN, RESNET_STD, resnet50_trunk
 from ..vggish import VGGish
 
@@ -110,24 +111,33 @@ class VisualFeatureExtractor(nn.Module):
     @staticmethod
     def _pass_inputs(frames, index, count, count_t, matrix):
         """The trunks' inputs of one pass of embed_shots: {(224, 224): uint8 [count,224,224,3], (299, 299): ...} of the
-        frames ``index[:count]``, read where they lie - BGR rows or NV12 surfaces - and resized by one launch; a trunk
-        whose input size is the frame size gets the gathered (and, for NV12, converted) frames themselves."""
-        nv12 = isinstance(frames, Nv12Frames)
+        frames ``index[:count]``, read where they lie - BGR rows, NV12 surfaces or the YUV 4:2:0 surfaces of a
+        yuv.YuvFrames - and resized by one launch; a trunk whose input size is the frame size gets the gathered (and, for
+        surfaces, converted) frames themselves."""
+        nv12, yuv = isinstance(frames, Nv12Frames), isinstance(frames, YuvFrames)
         h, w = frames.shape[1:3]
         sizes = [s for s in ((224, 224), (299, 299)) if s != (h, w)]
         if nv12:
             resized = dict(zip(sizes, nv12_resize_gather(frames, index, count, sizes, matrix)))
+        elif yuv:
+            resized = dict(zip(sizes, yuv_resize_gather(frames, index, count, sizes, matrix)))
         else:
             resized = dict(zip(sizes, ops.resize_gather(frames, index, count, sizes)))
         if len(sizes) < 2:
-            resized[(h, w)] = nv12_to_bgr(frames, index, count, matrix) if nv12 else ops.gather_rows(frames, index, count_t)
+            if nv12:
+                resized[(h, w)] = nv12_to_bgr(frames, index, count, matrix)
+            elif yuv:
+                resized[(h, w)] = yuv_to_bgr(frames, index, count, matrix)
+            else:
+                resized[(h, w)] = ops.gather_rows(frames, index, count_t)
         return resized
 
     def embed_shots(self, frames_u8, plan, matrix="bt601"):
         """forward for every shot of a ragged batch of videos: fp32 [S, 4096] on the device, row s what forward returns
         for the sampled frames of shot s of ``plan`` (an ops.StageOneTables; zeros for an empty shot).  ``frames_u8``:
-        device uint8 [N,h,w,3], the videos concatenated, or an ingest.Nv12Frames of them (converted by ``matrix`` as they
-        are read: the rows of embed_shots(nv12_to_bgr(frames), plan), bit for bit).  Per pass of the plan - whole BatchNorm
+        device uint8 [N,h,w,3], the videos concatenated, or an ingest.Nv12Frames or yuv.YuvFrames of them (converted by
+        ``matrix`` as they are read: the rows of embed_shots(nv12_to_bgr(frames), plan) or
+        embed_shots(yuv_to_bgr(frames), plan), bit for bit).  Per pass of the plan - whole BatchNorm
         groups of one size, so both trunks take their uniform forms - the pass's frames are gathered (and resized to 224x224 and 299x299 by one
         launch) straight from ``frames_u8``, and the two trunks write the pass's rows of one [F, 4096] buffer; two
         segment_mean_perm launches then average every shot's rows, in the order of its frames.  The BatchNorm groups are
@@ -136,6 +146,9 @@ class VisualFeatureExtractor(nn.Module):
         if isinstance(frames_u8, Nv12Frames):
             ops._device_arg(frames_u8.data, "frames.data", "embed_shots", (torch.uint8,), shape=(plan.frames, None, None),
                             device=plan.device)
+        elif isinstance(frames_u8, YuvFrames):
+            ops._device_arg(frames_u8.data, "frames.data", "embed_shots", (torch.uint8,),
+                            shape=(plan.frames,) + (None,) * (frames_u8.data.dim() - 1), device=plan.device)
         else:
             ops._device_arg(frames_u8, "frames", "embed_shots", (torch.uint8,), shape=(plan.frames, None, None, 3),
                             device=plan.device)
@@ -339,7 +352,8 @@ class AVProcessor:
         what process_decoded(frames of video v, waveforms[v], fps of video v, shots of video v, batch_audio=True) returns,
         in shapes and dtypes too (np.array([]) twice for a video without shots, a zero visual row for an empty shot).
         ``frames_u8``: uint8 [N,h,w,3], the videos concatenated - a device tensor, or a numpy array uploaded once - or an
-        ingest.Nv12Frames on the device (the decoder's surfaces, converted by ``matrix`` where they are read);
+        ingest.Nv12Frames or yuv.YuvFrames on the device (the decoder's surfaces - NV12, or I420 / P010 / ... -,
+        converted by ``matrix`` where they are read);
         ``video_offsets``: the host frame offsets [V + 1]; ``fps``: one number or one per video; ``shots``: one host
         [(start, end)] list per video, a features.shots.ShotBatchResult, or None to run detect_shots_batch.  The visual
         rows of all shots come from ONE VisualFeatureExtractor.embed_shots call (passes of at most ``chunk_frames``
@@ -347,11 +361,11 @@ class AVProcessor:
         from .shots import ShotBatchResult, detect_shots_batch
         if isinstance(frames_u8, np.ndarray):
             frames_u8 = torch.from_numpy(np.ascontiguousarray(frames_u8)).to(_device())
-        nv12 = isinstance(frames_u8, Nv12Frames)
+        nv12 = isinstance(frames_u8, (Nv12Frames, YuvFrames))
         data = frames_u8.data if nv12 else frames_u8
         if not torch.is_tensor(data) or not data.is_cuda:
-            raise ValueError("process_decoded_batch: frames must be a numpy array, a device tensor or Nv12Frames on the "
-                             "device")
+            raise ValueError("process_decoded_batch: frames must be a numpy array, a device tensor or Nv12Frames / "
+                             "YuvFrames on the device")
         if not nv12:
             frames_u8 = frames_u8.contiguous()
         if shots is None:

@@ -18,6 +18,7 @@ import torch
 
 from .. import ops
 from ..ingest import Nv12Frames, nv12_hsv_frame_diff_batch
+from ..yuv import YuvFrames, yuv_hsv_frame_diff_batch
 from ..ragged import exclusive_offsets
 
 DEFAULT_MIN_WIDTH = 256  # scenedetect.scene_manager.DEFAULT_MIN_WIDTH
@@ -147,24 +148,26 @@ def detect_shots_batch(frames_u8, video_offsets, threshold=27.0, min_scene_len=1
     offsets [V + 1] (or a prepared ops.ShotTables) -> ShotBatchResult.  Four kernels' worth of launches - the frame
     differences of all videos, one workgroup per video for the cuts, a scan, one workgroup per video for the tables -
     and no host round trip: the cut lists, the shot table, the sampled-frame table and the BatchNorm micro-batch table
-    stay on the device until ShotBatchResult.host().  ``frames_u8`` may be an ingest.Nv12Frames: the frame differences
-    then read the decoder's surfaces (converted by ``matrix`` on the way in, no BGR copy) and give the integers of the
-    converted frames; everything after them is the same launches."""
-    nv12 = isinstance(frames_u8, Nv12Frames)
-    data = frames_u8.data if nv12 else frames_u8
+    stay on the device until ShotBatchResult.host().  ``frames_u8`` may be an ingest.Nv12Frames or a yuv.YuvFrames (I420,
+    P010, ...): the frame differences then read the decoder's surfaces (converted by ``matrix`` on the way in, no BGR
+    copy) and give the integers of the converted frames; everything after them is the same launches."""
+    nv12, yuv = isinstance(frames_u8, Nv12Frames), isinstance(frames_u8, YuvFrames)
+    data = frames_u8.data if nv12 or yuv else frames_u8
     if not torch.is_tensor(data) or not data.is_cuda:
         raise ValueError("detect_shots_batch: frames must be a device tensor (there is no CPU fallback)")
     plan = video_offsets if isinstance(video_offsets, ops.ShotTables) else \
         ops.ShotTables(video_offsets, min_scene_len, data.device)
     if plan.min_scene_len != int(min_scene_len):
         raise ValueError(f"detect_shots_batch: the tables were built for min_scene_len {plan.min_scene_len}")
-    if not nv12:
+    if not (nv12 or yuv):
         frames_u8 = frames_u8.contiguous()
     h, w = frames_u8.shape[1:3]
     step = downscale_factor(w) if step is None else int(step)
     pixels = float(len(range(0, h, step)) * len(range(0, w, step)))
     if nv12:
         sums = nv12_hsv_frame_diff_batch(frames_u8, plan, step, raw=True, matrix=matrix)
+    elif yuv:
+        sums = yuv_hsv_frame_diff_batch(frames_u8, plan, step, raw=True, matrix=matrix)
     else:
         sums = ops.hsv_frame_diff_batch(frames_u8, plan, step, raw=True)
     cuts, totals = ops.shot_cuts_batch(plan, sums, pixels, threshold)
