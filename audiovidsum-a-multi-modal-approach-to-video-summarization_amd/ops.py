@@ -13,8 +13,8 @@ from ._abi import (ACT_NONE, ACT_RELU, AVS_BF16, AVS_F16X2, AVS_F32, AVS_F32_SPL
                    lib)
 from .ragged import (ATTN_BWD_TILE, ATTN_FWD_TILE, AttnTable, EVAL_CHUNK, EVAL_COLS, EVAL_MAX_T, EVAL_TILE, FUSION_MAX_N, FUSION_MID_L, FUSION_SMALL_L,  # noqa: F401
                      KTS_MAX_SAMPLES, SHOT_INTERVAL, SHOT_MAX_FRAMES, SHOT_MICRO_BATCH, SUMMARY_MAX_CAPACITY, SUMMARY_MAX_ROWS,
-                     EvalTables, FusionTables, KtsTables, RaggedOffsets, RankTables, SeqTable, ShotTables, StageOneTables,
-                     SummaryTables)
+                     EvalTables, FusionTables, KtsTables, RaggedOffsets, RankTables, RenderTables, SeqTable, ShotTables,
+                     StageOneTables, SummaryTables)
 
 __all__ = [
     "ACT_NONE", "ACT_RELU", "linear", "gemm_nt_batched", "conv2d", "conv2d_raw", "conv2d_split", "conv_bnlocal_tile_rows", "conv_bncluster_ok", "conv_bnstats_ok", "cluster_exchange_errors", "lstm_split_errors", "conv1x1_bn", "conv1x1_gram_bn", "bn_gram_affine", "gram_supported", "frames_normalize", "pull_copy", "stem_conv_bn_pool", "stem_h2_operands", "stem_conv_pool_h2", "resize_bilinear",
@@ -24,6 +24,7 @@ __all__ = [
     "SeqTable", "seq_shift_rows", "seq_mse",
     "AttnTable",
     "RankTables",
+    "RenderTables",
     "ShotTables", "hsv_frame_diff_batch", "shot_cuts_batch", "shot_tables", "gather_rows",
     "SummaryTables", "shot_value_sums", "knapsack_batch", "mask_overlap_counts",
     "StageOneTables", "resize_gather", "segment_mean_perm",

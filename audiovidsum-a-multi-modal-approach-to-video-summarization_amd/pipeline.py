@@ -330,6 +330,31 @@ class FrameScoringPipeline:
         return keyshot_summaries_device(scores, video_offsets, shots, ratio)
 
     @staticmethod
+    def render_device(frames, video_offsets, selection, wave=None, wave_offsets=None, fps=None, out=None, fade=0, row=0,
+                      matrix="bt601", sr=16000):
+        """The summary itself, on the device: the picked frames in a form an encoder takes and the matching audio,
+        nothing read back.  ``frames``: the batch's uint8 BGR tensor [N, h, w, 3], ingest.Nv12Frames or yuv.YuvFrames;
+        ``selection``: the KeyshotResult of summarize_device (row ``row`` of its mask is rendered, at the capacities
+        of its plan) or a uint8 device mask [N] such as select_device's.  ``out``: None (the source's format), "bgr" or
+        a YuvFrames describing the destination (render.summary_frames).  With ``wave`` (fp32 device [S], the tracks
+        concatenated), ``wave_offsets`` (host [V + 1]) and ``fps`` (one number or one per video) the runs' samples are
+        cut as well, with a linear ``fade`` of that many samples at both ends of every run.  Returns a
+        render.SummaryRender; its host() is the one download of the small tables."""
+        from . import render
+        audio = wave is not None
+        kw = dict(wave_offsets=wave_offsets, fps=fps, sr=sr) if audio else {}
+        if isinstance(selection, torch.Tensor):
+            tables = ops.RenderTables(video_offsets, device=selection.device, **kw)
+        else:
+            tables = ops.RenderTables.from_keyshots(selection, **kw)
+            if not np.array_equal(tables.offsets, np.asarray(video_offsets, dtype=np.int64).reshape(-1)):
+                raise ValueError("render_device: the selection was made for other video offsets")
+        index = render.summary_index(selection, tables, row)
+        picked = render.summary_frames(frames, index, out, matrix)
+        cut, cut_offsets = render._audio_cut(wave, index, tables, fade, None) if audio else (None, None)
+        return render.SummaryRender(index, picked, cut, cut_offsets)
+
+    @staticmethod
     def segment_device(features, video_offsets, **kw):
         """Kernel temporal segmentation of every video on its per-frame embeddings (embed()'s [N, 4096], where they
         lie): features.kts.kts_batch_device with its keywords (stride, ncp, vmax, lmin, select).  Returns the

@@ -1,6 +1,6 @@
 """Host plans of the ragged-batch layers: row offsets validated on the host and uploaded once (RaggedOffsets and the
-eight tables built on it - EvalTables, SeqTable, AttnTable, ShotTables, StageOneTables, SummaryTables, KtsTables,
-RankTables) and the
+nine tables built on it - EvalTables, SeqTable, AttnTable, ShotTables, StageOneTables, SummaryTables, KtsTables,
+RankTables, RenderTables) and the
 pair tables of the batched fusion (FusionTables).
 Pure host code on numpy and torch: nothing here touches the kernel library, so the plans can be built and checked with
 ``device="cpu"`` where there is no GPU.  ops.py re-exports every name and holds the launch wrappers that take them."""
@@ -10,6 +10,7 @@ import torch
 from ._attn_abi import load_header as _load_attn_header   # (the header's reader only: the library is not loaded here)
 from ._header import load as _load_header
 from ._loss_abi import load_header as _load_loss_header   # (again the reader only)
+from ._render_abi import load_header as _load_render_header   # (again the reader only)
 from .features.kts import KTS_MAX_SAMPLES, kts_penalties   # (pure numpy: the limit and the penalty of the definitions)
 
 # The sizes the tables below share with the kernels that read them are the header's (include/avsum_hip.h, where each is
@@ -52,6 +53,12 @@ _HL = _load_loss_header().constants
 RANK_TILE = _HL["AVSL_TILE"]                 # 256: rows of a video per workgroup of the pair kernel
 RANK_MAX_T = _HL["AVSL_MAX_T"]               # 32768: rows of one video (pair counts: < 2^30 per row, < 2^31 per video)
 _RANK_TILE_COLS = _HL["AVSL_TILE_COLS"]      # 2: int32 per row of the tile table
+
+# include/avsum_render.h: the tile of the summary index and its limits
+_HR = _load_render_header().constants
+RENDER_TILE = _HR["AVSR_TILE"]               # 1024: frames of a video per workgroup of the summary index
+RENDER_MAX_FRAMES = _HR["AVSR_MAX_FRAMES"]   # 2^24: frames of one batch
+_RENDER_TILE_COLS = _HR["AVSR_TILE_COLS"]    # 2: int32 per row of the tile table
 
 
 def exclusive_offsets(lengths):
@@ -438,6 +445,90 @@ class RankTables(RaggedOffsets):
             -1, _RANK_TILE_COLS)
         self.ntiles = self.tiles.shape[0]
         self.tiles_t, = _upload(self.device, self.tiles)
+
+
+class RenderTables(RaggedOffsets):
+    """The host plan of one batch layout for rendering a summary (render.summary_index, summary_frames, summary_audio),
+    built once from the host frame offsets [V + 1] of the videos in the concatenated frames and the capacities of the
+    buffers the summary is written to - host numbers, so that no launch waits for a count.
+
+    ``capacity``: int64 [V], the most frames a summary of video v may hold (a SummaryTables' ``capacity``; None: the
+    whole video, for a bare mask).  ``frame_cap``: entries of the frame list (default: sum(capacity), N for a bare
+    mask).  ``run_cap``: rows of the run table (default ceil(N / 2) + V: a video of n frames has at most ceil(n / 2)
+    runs; from_keyshots passes the shot capacity, since a run is one or more whole shots).  Both at least 1.
+    Audio (all three of ``wave_offsets``, ``fps`` given, ``sr``): ``wave_offsets`` the host sample offsets [V + 1] of the
+    tracks in the concatenated waveform (start at 0, do not decrease), ``fps`` one number or one per video, converted
+    to float64 HERE and uploaded with the plan, ``sr`` the sample rate.  ``sample_cap`` (None: computed) bounds the
+    summary's samples.  DERIVED, not measured: a run (s, e) of video v holds floor(e / fps * sr) - floor(s / fps * sr)
+    < (e - s) * sr / fps + 1 samples in exact arithmetic, the runs of v hold at most capacity[v] frames together and
+    there are at most R_v = min(capacity[v], ceil(n_v / 2)) of them, and no run leaves the track, so video v holds at
+    most min(len_v, ceil(capacity[v] * sr / fps_v) + R_v + 1) samples; the last + 1 absorbs the float64 rounding of the
+    two bounds of every run, which sums to less than one sample while R_v * n_v * sr / fps_v < 2^50.  sample_cap is the
+    sum over the videos, and S, the whole waveform, for a bare mask.  Every store is guarded by its capacity on the
+    device whatever the bound.
+
+    Host side (numpy): ``offsets``, ``lengths``, ``nvideos``, ``frames``, ``bare`` (no capacity was given),
+    ``capacity``, ``frame_cap``, ``run_cap``,
+    ``tiles`` int32 [ntiles, 2] = (video, tile of 1024 frames) - every video's tiles, video after video -, ``ntiles``;
+    with audio ``wave_offsets``, ``fps`` float64 [V], ``sr``, ``samples`` (= wave_offsets[-1]), ``sample_cap``.
+    Device side: ``offsets_t``, ``tiles_t``; with audio ``wave_offsets_t``, ``fps_t``.  ``device="cpu"`` keeps everything
+    on the host (the builder can be checked without a GPU or the library).  Refused, each with a ValueError: what
+    ShotTables refuses about the offsets (more than 2^24 frames among it), a capacity of another length than V or
+    negative, frame_cap or run_cap below 1, wave offsets of another length, not starting at 0 or decreasing, an fps or
+    sr that is not finite and positive, wave_offsets without fps or the reverse."""
+
+    def __init__(self, offsets_host, frame_cap=None, run_cap=None, capacity=None, wave_offsets=None, fps=None, sr=16000,
+                 sample_cap=None, device=None):
+        super().__init__(offsets_host, "RenderTables", device=device, max_total=RENDER_MAX_FRAMES, total_inclusive=True)
+        self.nvideos, self.frames = self.count, self.total
+        bare = capacity is None
+        capacity = self.lengths.copy() if bare else np.array(capacity, dtype=np.int64).reshape(-1)
+        if capacity.size != self.nvideos or (capacity < 0).any():
+            raise ValueError(f"RenderTables: capacity must hold one non-negative entry per video ({self.nvideos})")
+        self.bare, self.capacity = bare, np.minimum(capacity, self.lengths)
+        self.frame_cap = max(int(self.capacity.sum()), 1) if frame_cap is None else int(frame_cap)
+        self.run_cap = -(-self.frames // 2) + self.nvideos if run_cap is None else int(run_cap)
+        if self.frame_cap < 1 or self.run_cap < 1:
+            raise ValueError(f"RenderTables: frame_cap and run_cap must be >= 1, got {self.frame_cap} and {self.run_cap}")
+        self.tiles = np.stack(segment_tiles(-(-self.lengths // RENDER_TILE)), 1).astype(np.int32).reshape(
+            -1, _RENDER_TILE_COLS)
+        self.ntiles = self.tiles.shape[0]
+        self.tiles_t, = _upload(self.device, self.tiles)
+        self.has_audio = wave_offsets is not None
+        if self.has_audio != (fps is not None):
+            raise ValueError("RenderTables: wave_offsets and fps come together")
+        if not self.has_audio:
+            self.wave_offsets = self.fps = self.sr = self.samples = self.sample_cap = None
+            return
+        tracks = RaggedOffsets(wave_offsets, "RenderTables: wave_offsets", device=self.device, min_length=0,
+                               max_total=1 << 62)
+        if tracks.count != self.nvideos:
+            raise ValueError(f"RenderTables: {tracks.count} tracks for {self.nvideos} videos")
+        fps = np.array(fps, dtype=np.float64).reshape(-1)
+        fps = np.repeat(fps, self.nvideos) if fps.size == 1 else fps
+        self.sr = float(sr)
+        if fps.size != self.nvideos or not (np.isfinite(fps).all() and (fps > 0).all()):
+            raise ValueError(f"RenderTables: fps must be one finite positive number, or one per video ({self.nvideos})")
+        if not (np.isfinite(self.sr) and self.sr > 0):
+            raise ValueError(f"RenderTables: sr must be finite and positive, got {sr}")
+        self.wave_offsets, self.wave_offsets_t, self.fps, self.samples = tracks.offsets, tracks.offsets_t, fps, tracks.total
+        self.fps_t, = _upload(self.device, fps)
+        runs = np.minimum(self.capacity, -(-self.lengths // 2))
+        per_video = np.minimum(tracks.lengths, np.ceil(self.capacity * self.sr / fps).astype(np.int64) + runs + 1)
+        if sample_cap is None:
+            sample_cap = self.samples if bare else int(per_video.sum())
+        self.sample_cap = max(int(sample_cap), 1)
+
+    @classmethod
+    def from_keyshots(cls, plan, **kw):
+        """The plan for rendering row(s) of the KeyshotResult computed with ``plan`` (a SummaryTables, or the result
+        itself): frame_cap = plan.capacity.sum(), run_cap = plan.shot_cap, on the plan's device; ``kw``: the audio
+        arguments."""
+        plan = getattr(plan, "plan", plan)
+        if not isinstance(plan, SummaryTables):
+            raise ValueError("RenderTables.from_keyshots: plan must be a SummaryTables or a KeyshotResult")
+        return cls(plan.offsets, max(int(plan.capacity.sum()), 1), plan.shot_cap, plan.capacity,
+                   device=kw.pop("device", plan.device), **kw)
 
 
 class FusionTables:
