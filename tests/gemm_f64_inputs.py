@@ -395,20 +395,25 @@ def bf16_half_step(ref):
     return torch.where(ref == 0, torch.zeros_like(ref), torch.ldexp(torch.ones_like(ref), exp - 9))
 
 
+def fp32_term(e32, s):
+    """The fp32 bound's form: 4 * e32 (the fp32 CPU evaluation's largest error in the row) + 8 * eps32 * S."""
+    return 4.0 * e32 + 8.0 * EPS32 * s
+
+
 @functools.lru_cache(maxsize=8)
 def bundle(case, which):
     """(ref, target, bound, e32 per row, S) of a case and operand set, float64 [batch, rows, N], computed once and shared;
     a result must lie within ``bound`` of ``target``: the reference, for AVS_F32_SPLIT its restatement."""
     ref, s = reference(case, which), magnitude(case, which)
     e32 = (fp32_yardstick(case, which) - ref).abs().amax(-1, keepdim=True) if ref.numel() else ref.new_zeros(ref.shape[:2] + (1,))
-    fp32_term = 4.0 * e32 + 8.0 * EPS32 * s
+    term = fp32_term(e32, s)
     if case.dtype == ACC64:
         return ref, ref, 8.0 * EPS32 * s, e32, s
     if case.dtype == BF16:
-        return ref, ref, bf16_half_step(ref) + fp32_term, e32, s
+        return ref, ref, bf16_half_step(ref) + term, e32, s
     if case.dtype == SPLIT:
-        return ref, restatement(case, which), fp32_term, e32, s
-    return ref, ref, fp32_term, e32, s
+        return ref, restatement(case, which), term, e32, s
+    return ref, ref, term, e32, s
 
 
 def split_ratio(case, which):

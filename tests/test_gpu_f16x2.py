@@ -12,6 +12,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from f16x2_format import emu_pack, emu_unpack  # noqa: F401  (the format restated on the CPU; other modules import it from here)
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
@@ -20,23 +22,6 @@ TOL = 1e-5
 def _ops():
     from avsum_amd import ops
     return ops
-
-
-def emu_pack(x):
-    """fp32 [..., C] (C % 8 == 0) -> float32-typed tensor of the same shape holding the AVS_F16X2 slots."""
-    x = x.float().contiguous()
-    c = x.shape[-1]
-    assert c % 8 == 0
-    xc = x.clamp(-65504.0, 65504.0)
-    hi = xc.half()
-    lo = (xc - hi.float()).half()
-    runs = torch.stack([hi.reshape(-1, 8), lo.reshape(-1, 8)], 1).contiguous()   # [runs, 2, 8] halves = 32 bytes
-    return runs.view(torch.float32).reshape(x.shape)
-
-
-def emu_unpack(p):
-    runs = p.contiguous().view(torch.float16).reshape(-1, 2, 8).float()
-    return (runs[:, 0] + runs[:, 1]).reshape(p.shape)
 
 
 def test_pack_unpack_bit_exact(dev):
