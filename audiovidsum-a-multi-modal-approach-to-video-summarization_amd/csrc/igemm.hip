@@ -2422,7 +2422,7 @@ static int bnlocal_plan(const avs_conv_desc* d, int64_t rpg, IgemmParams& p, con
                   per_tile * rpg * 4 >= 256 * 3 && per_tile <= BNLOCAL_MAX_GROUPS && (long long)p.K * es > 128 &&
                   d->alpha == 1.0f && (p.ldc * es) % (h2 ? 32 : 16) == 0;
   AVS_REQUIRE(ok, AVS_E_UNSUPPORTED,
-              "%s: needs bf16 / f16x2, cout a multiple of %d, equal groups of 43..256 rows that fill 3/4 of a 256-row "
+              "%s: needs bf16 / f16x2, cout a multiple of %d, equal groups of 37..256 rows that fill 3/4 of a 256-row "
               "tile, a reduction of more than 128 bytes, aligned output rows", who, bn);
   p.tiles_n = p.N / bn;
   p.tile_rows = (int)(per_tile * rpg);

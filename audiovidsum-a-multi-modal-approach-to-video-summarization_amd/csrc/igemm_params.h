@@ -81,7 +81,7 @@ struct IgemmParams {
 };
 
 enum { EPI_PLAIN = 0, EPI_STATS = 1, EPI_ANY = 2, EPI_BRELU = 3, EPI_BNLOCAL = 5, EPI_AFFINE = 6 };
-constexpr int BNLOCAL_MAX_GROUPS = 6;  // groups per 256-row tile (rows_per_group >= 43)
+constexpr int BNLOCAL_MAX_GROUPS = 6;  // groups per 256-row tile (rows_per_group >= 37: six groups of 37 .. 42 rows)
 constexpr int STATS_MIN_GROUP_ROWS = 64;  // EPI_STATS: a wave's 64 rows then overlap at most two groups
 constexpr int XIN_TABLE_MIN_GROUP_ROWS = 384;  // XIN: the nine-tap form's 384 buffer rows then touch at most two groups
 constexpr int XIN_TABLE_MAX_CIN = 128;         // ... and the two groups' affines fit the LDS table (2 x cin x 2 floats)

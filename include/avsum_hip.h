@@ -234,7 +234,7 @@ int avs_conv2d_nhwc_bnstats_xin(const avs_conv_desc* desc, const void* d_x, cons
  * raw in HBM.  Replaces avs_conv2d_nhwc_bnstats + avs_bn_apply for the 14x14 / 7x7 layers of the train-mode
  * ResNet trunk (features/extractors.py:29,65).
  * avs_conv2d_bnlocal_tile_rows returns the rows of a tile that are used (> 0) when the shape takes this form, or
- * AVS_E_UNSUPPORTED: not bf16; cout not a multiple of the column tile; groups of fewer than 43 or more than 256
+ * AVS_E_UNSUPPORTED: not bf16; cout not a multiple of the column tile; groups of fewer than 37 or more than 256
  * rows or filling less than 3/4 of a tile; a reduction of at most 128 bytes; unaligned output rows.          */
 int avs_conv2d_bnlocal_tile_rows(const avs_conv_desc* desc, int64_t rows_per_group);
 int avs_conv2d_nhwc_bnlocal(const avs_conv_desc* desc, const void* d_x, const void* d_w, void* d_y,
